@@ -12,13 +12,17 @@ token as llama-bench does (llama_decode + llama_synchronize).  The context grows
 --launch graph: the quantized matmuls alone, one launch per step (129), captured in a hipGraph (round 1's path, no glue).
 Weights, KV cache and the token embedding input are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]         (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]         (N>1: launched by torch.distributed.run)
 
 N>1 = the reference's --split-mode layer: contiguous layer ranges per GPU, the [1, n_embd] f32 activation
 handed to the next stage with an RCCL send/recv; a token visits the stages in order (strong scaling: the
 curve measures hop overhead).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0): the tg figure of the timed steps (`value`, `ms_per_step`).  A plain run does only that: set-up, warm-up,
+the timed steps, the outputs (--dump-outputs) and the line.  --full adds what needs runs of its own: the check of the plan against the
+node-by-node path, `roofline` (per-kernel timings), `pp512`, `cpu_baseline`, `graph_compute` and `llama_bench` (and with it `vs_baseline`).
+--dump-outputs DIR: what the timed path handed back in its last step, as DIR/<name>.npy (float32); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -55,6 +59,9 @@ def parse():
     ap.add_argument("--no-llama-bench", action="store_true", help="skip the leg that runs the reference's own llama-bench through the plugin and on the CPU backend")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline sample")
     ap.add_argument("--dry-run", action="store_true", help="plumbing only (CPU/gloo test of the N>1 hop protocol): no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also the plan check, roofline, pp512, CPU baseline, plugin and llama-bench legs (off: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -90,6 +97,7 @@ class Stage:
     def __init__(self, torch, g, specs, fuse, device):
         self.torch, self.g = torch, g
         self.groups = []         # (list[QWeight], x tensor, list[y tensors], bytes a token reads, ids tensor or None)
+        self.id_out = {}         # weight name -> the y of its last MUL_MAT_ID
         self.bytes = 0
         self.has_moe = any(s.n_expert > 1 for s in specs)
         xs = {}
@@ -205,7 +213,7 @@ class Stage:
         g = self.g
         ws, x, ys, _, ids = grp
         if ids is not None:
-            g.mul_mat_id(ws[0], x, ids)
+            self.id_out[ws[0].name] = g.mul_mat_id(ws[0], x, ids)
         elif len(ws) == 1:
             g.mul_mat(ws[0], x, out=ys[0])
         else:
@@ -215,6 +223,16 @@ class Stage:
         for grp in self.groups:
             self.run_group(grp)
 
+    def outputs(self):
+        """What the per-matmul launch path hands back from its last run, by weight name."""
+        out = {}
+        for ws, _, ys, _, _ in self.groups:
+            if ys is None:
+                out[ws[0].name] = self.id_out[ws[0].name]
+            else:
+                out.update((w.name, y) for w, y in zip(ws, ys))
+        return out
+
 
 def kernel_source_sha16():
     """Hash of the sources of the dominant kernel (ties a committed PMC traffic figure to the code it was measured on)."""
@@ -223,6 +241,23 @@ def kernel_source_sha16():
     for f in ("plan.hip", "gemv_stream.cuh", "act_quant.cuh", "mi355q_common.h"):
         h.update((ROOT / "llama.cpp.dsp_amd" / "csrc" / f).read_bytes())
     return h.hexdigest()[:16]
+
+
+DUMP_MAX_BYTES = 60_000_000      # the .npy payloads of one --dump-outputs, headers aside (64 MB in all)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32.  Past DUMP_MAX_BYTES in all, every array is cut to a seeded sample of its
+    elements (flattened, the same indices in every run) in proportion to its size."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, v.size * DUMP_MAX_BYTES // total)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(out_dir / f"{name}.npy", v)
 
 
 def measured_hbm_read_GBps(torch, device):
@@ -411,6 +446,7 @@ def main():
     import ggml_mi355 as g
     from ggml_mi355 import workloads as wl
     rehearse = os.environ.get("MI355Q_BENCH_REHEARSE") == "1" and not a.dry_run
+    torch.manual_seed(rank)                                     # weights, activations, norm weights: the same in every run
 
     def p2p_send(t, dst):
         dist.send(t.cpu() if rehearse else t, dst=dst)
@@ -482,7 +518,7 @@ def main():
             if rank == 0:
                 act.copy_(torch.randn_like(act))                # the token embedding (GET_ROWS of token_embd runs on the CPU in llama.cpp)
             plan = stage.make_decode_plan(cfg, act, n_ctx, rank == world - 1)
-            if world == 1:
+            if world == 1 and a.full:
                 verify_token0(torch, g, stage, plan, cfg, act)
         act_out = torch.zeros_like(act)
         done = torch.zeros(1, dtype=torch.int32, device=device)
@@ -536,6 +572,15 @@ def main():
         if rank == world - 1 and not a.dry_run and getattr(stage, "logits", None) is not None:
             if not bool(torch.isfinite(stage.logits).all()):
                 raise RuntimeError("the last stage's logits are not finite")
+    if a.dump_outputs and not a.dry_run:
+        # what a caller of the timed path receives: the plan's logits (llama_decode's host copy) on the last rank and the boundary
+        # activation on the others; the per-matmul launch paths hand back every matmul output
+        if plan is None:
+            dump_outputs(Path(a.dump_outputs), stage.outputs())
+        elif logits_host is not None:
+            dump_outputs(Path(a.dump_outputs), {"logits": logits_host})
+        else:
+            dump_outputs(Path(a.dump_outputs), {f"boundary_rank{rank}": act_out})
 
     out = {
         "metric": "llama-bench tg128 tok/s (decode step at the C-ABI of the quantized-matmul hot path), " + {"llama3-8b": "Llama-3-8B", "llama3-70b": "Llama-3-70B", "mixtral-8x7b": "Mixtral-8x7B"}[a.model] + " " + a.ftype,
@@ -553,7 +598,7 @@ def main():
                    "parallelism": "single GPU" if world == 1 else f"layer split over {world} GPUs (RCCL send/recv of the boundary activation; a token starts when the previous one has left the last GPU, as llama_synchronize makes llama-bench wait)"},
     }
 
-    if not a.dry_run and rank == 0:
+    if a.full and not a.dry_run and rank == 0:
         # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream ----
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         def timed(fn, reps):
@@ -688,17 +733,19 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     if not a.dry_run:
-        # Explicit, ordered teardown (nothing that owns HIP resources is left to interpreter exit / library finalizers): launch graphs and
-        # events first, then the plan, the weights, the cached workspaces; synchronize; unload the HIP library while the runtime is alive.
+        # Explicit, ordered teardown (nothing that owns HIP resources is left to interpreter exit): launch graphs and events first, then
+        # the plan, the weights, the binding's cached workspaces; synchronize.  libmi355q.so itself stays loaded until the process exits,
+        # as in every test process (the exit-time fault under rocprofv3 that once made this unload it came from the cooperative launch
+        # API, since removed: DESIGN.md section 5.6).
         import gc
         if plan is not None:
             plan.close()
         graph = plan = run_token = token = None
         stage.groups.clear(); stage = None
+        g._ws_cache.clear()
         gc.collect()
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-        g.shutdown()
         if os.environ.get("MI355Q_LOG_MAPS"):                   # attribution of exit-time frames (diagnostic)
             Path(os.environ["MI355Q_LOG_MAPS"]).write_text(Path("/proc/self/maps").read_text())
 

@@ -27,17 +27,17 @@ def row_size(t: int, k: int) -> int:
     return k // BLCK[t] * _F16_FIELDS[t][0]
 
 
-def random_blocks(t: int, nrows: int, k: int, rng: np.random.Generator) -> np.ndarray:
+def random_blocks(t: int, nrows: int, k: int, rng: np.random.Generator, scale: float = 1.0) -> np.ndarray:
     bs, fields = _F16_FIELDS[t]
     nb = k // BLCK[t]
     w = rng.integers(0, 256, (nrows, nb, bs), dtype=np.uint8)
     for off in fields:
-        scale = rng.uniform(1e-3, 5e-2, (nrows, nb)).astype(np.float16)
+        d = (rng.uniform(1e-3, 5e-2, (nrows, nb)) * scale).astype(np.float16)
         if rng.random() < 0.5:
-            scale = -scale if off == 0 and t in (oracle.Q6_K, oracle.Q3_K) else scale   # signed super-scales occur in practice
-        w[:, :, off:off + 2] = scale.view(np.uint8).reshape(nrows, nb, 2)
+            d = -d if off == 0 and t in (oracle.Q6_K, oracle.Q3_K) else d   # signed super-scales occur in practice
+        w[:, :, off:off + 2] = d.view(np.uint8).reshape(nrows, nb, 2)
     if t == oracle.IQ1_M:
-        h = rng.uniform(1e-3, 5e-2, (nrows, nb)).astype(np.float16).view(np.uint16)
+        h = (rng.uniform(1e-3, 5e-2, (nrows, nb)) * scale).astype(np.float16).view(np.uint16)
         for i in range(4):       # nibble i of the half lives in bits 12..15 of scales[i]
             w[:, :, 49 + 2 * i] = (w[:, :, 49 + 2 * i] & 0x0f) | ((((h >> (4 * i)) & 0xf) << 4).astype(np.uint8))
     return w.reshape(nrows, nb * bs)
@@ -47,7 +47,7 @@ def quantized_weights(t: int, nrows: int, k: int, rng: np.random.Generator, scal
     if oracle.ref_available("scalar") and nrows * k <= (1 << 24):
         ref = _ref()
         return ref.quantize(t, (rng.uniform(-1, 1, (nrows, k)) * scale).astype(np.float32))
-    return random_blocks(t, nrows, k, rng)
+    return random_blocks(t, nrows, k, rng, scale)       # (scale shrinks the block scales alike: chained products stay finite)
 
 
 _REF = None

@@ -1,43 +1,44 @@
-# Round-end GPU pass (run through gpurun): parity tests, smoke, bench, rocprofv3 kernel-trace and FETCH_SIZE passes, summaries under profiles/.
+# Round-end GPU pass: parity tests, smoke, bench, rocprofv3 kernel-trace and FETCH_SIZE passes, summaries under profiles/; logs under $OUT.
 # Every step must succeed: a failing step stops the pass with its exit code (no "|| echo").
 TAG=${TAG:-round2}
+OUT=${OUT:-build/round_end}
 cd $GRAFT_REPO_ROOT || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+mkdir -p $OUT
 step() { echo "== $*"; }
 if [ -z "$SKIP_TESTS" ]; then
   step "pytest -m gpu"
-  timeout -k 10 1100 python -m pytest tests -m gpu -x -q > gpurun_out/gpu_tests_full.log 2>&1; rc=$?
-  tail -3 gpurun_out/gpu_tests_full.log | cut -c1-300
-  [ $rc -ne 0 ] && { tail -60 gpurun_out/gpu_tests_full.log | cut -c1-300; exit $rc; }
+  timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests_full.log 2>&1; rc=$?
+  tail -3 $OUT/gpu_tests_full.log | cut -c1-300
+  [ $rc -ne 0 ] && { tail -60 $OUT/gpu_tests_full.log | cut -c1-300; exit $rc; }
 fi
 step "smoke"
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; rc=$?; tail -2 gpurun_out/smoke.log; [ $rc -ne 0 ] && exit $rc
-step "bench.py (default)"
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err; rc=$?
-[ $rc -ne 0 ] && { tail -20 gpurun_out/bench_$TAG.err; exit $rc; }
-cut -c1-400 gpurun_out/bench_$TAG.json
-rm -rf gpurun_out/prof_kt gpurun_out/prof_pmc
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?; tail -2 $OUT/smoke.log; [ $rc -ne 0 ] && exit $rc
+step "bench.py --full"
+timeout -k 10 600 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
+[ $rc -ne 0 ] && { tail -20 $OUT/bench_$TAG.err; exit $rc; }
+cut -c1-400 $OUT/bench_$TAG.json
+rm -rf $OUT/prof_kt $OUT/prof_pmc
 step "rocprofv3 --kernel-trace --stats"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_kt -- python3 bench.py --steps 32 --warmup 4 --no-cpu-baseline > gpurun_out/prof_kt.log 2>&1; rc=$?
-echo "rocprofv3 kernel-trace pass: exit $rc"; [ $rc -ne 0 ] && { tail -20 gpurun_out/prof_kt.log; exit $rc; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt -- python3 bench.py --steps 32 --warmup 4 --full --no-cpu-baseline > $OUT/prof_kt.log 2>&1; rc=$?
+echo "rocprofv3 kernel-trace pass: exit $rc"; [ $rc -ne 0 ] && { tail -20 $OUT/prof_kt.log; exit $rc; }
 step "rocprofv3 --pmc FETCH_SIZE (own pass)"
-timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof_pmc -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-pp > gpurun_out/prof_pmc.log 2>&1; rc=$?
-echo "rocprofv3 pmc pass: exit $rc"; [ $rc -ne 0 ] && { tail -20 gpurun_out/prof_pmc.log; exit $rc; }
-python tools/summarize_profile.py $TAG gpurun_out/prof_kt gpurun_out/prof_pmc || exit 1
+timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_pmc -- python3 bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-pp > $OUT/prof_pmc.log 2>&1; rc=$?
+echo "rocprofv3 pmc pass: exit $rc"; [ $rc -ne 0 ] && { tail -20 $OUT/prof_pmc.log; exit $rc; }
+python tools/summarize_profile.py $TAG $OUT/prof_kt $OUT/prof_pmc || exit 1
 step "bench.py again: the roofline now quotes the traffic measured on these sources"
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err; rc=$?
-[ $rc -ne 0 ] && { tail -20 gpurun_out/bench_$TAG.err; exit $rc; }
-cp gpurun_out/bench_$TAG.json profiles/${TAG}_bench.json
+timeout -k 10 600 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
+[ $rc -ne 0 ] && { tail -20 $OUT/bench_$TAG.err; exit $rc; }
+cp $OUT/bench_$TAG.json profiles/${TAG}_bench.json
 python3 - <<EOF
-import json; j = json.load(open("gpurun_out/bench_$TAG.json"))
+import json; j = json.load(open("$OUT/bench_$TAG.json"))
 print("value", j["value"], j["unit"], "| roofline", {k: j["roofline"][k] for k in ("achieved", "frac", "traffic", "avg_launch_us")}, "| pp512", j.get("pp512", {}).get("value"),
       "| cpu", (j.get("cpu_baseline") or {}).get("value"), "| graph_compute", {k: (j.get("graph_compute") or {}).get(k) for k in ("value", "us_per_token")})
 EOF
 step "other configurations"
-timeout -k 10 300 python bench.py --ftype Q8_0 --no-cpu-baseline > profiles/${TAG}_bench_llama8b_q8_0.json 2> gpurun_out/bench_q8.err; rc=$?; [ $rc -ne 0 ] && { tail gpurun_out/bench_q8.err; exit $rc; }
-timeout -k 10 500 python bench.py --model mixtral-8x7b --no-cpu-baseline --steps 32 --warmup 4 > profiles/${TAG}_bench_mixtral8x7b.json 2> gpurun_out/bench_mx.err; rc=$?; [ $rc -ne 0 ] && { tail gpurun_out/bench_mx.err; exit $rc; }
-timeout -k 10 500 python bench.py --model llama3-70b --no-cpu-baseline --steps 32 --warmup 4 > profiles/${TAG}_bench_llama70b_1gpu.json 2> gpurun_out/bench_70.err; rc=$?; [ $rc -ne 0 ] && { tail gpurun_out/bench_70.err; exit $rc; }
+timeout -k 10 300 python bench.py --ftype Q8_0 --full --no-cpu-baseline > profiles/${TAG}_bench_llama8b_q8_0.json 2> $OUT/bench_q8.err; rc=$?; [ $rc -ne 0 ] && { tail $OUT/bench_q8.err; exit $rc; }
+timeout -k 10 500 python bench.py --model mixtral-8x7b --full --no-cpu-baseline --steps 32 --warmup 4 > profiles/${TAG}_bench_mixtral8x7b.json 2> $OUT/bench_mx.err; rc=$?; [ $rc -ne 0 ] && { tail $OUT/bench_mx.err; exit $rc; }
+timeout -k 10 500 python bench.py --model llama3-70b --full --no-cpu-baseline --steps 32 --warmup 4 > profiles/${TAG}_bench_llama70b_1gpu.json 2> $OUT/bench_70.err; rc=$?; [ $rc -ne 0 ] && { tail $OUT/bench_70.err; exit $rc; }
 python3 - <<EOF
 import json
 for f in ("llama8b_q8_0", "mixtral8x7b", "llama70b_1gpu"):
@@ -49,8 +50,8 @@ MP=oracle/_ref/avx2/model_parity
 MPS=oracle/_ref/scalar/model_parity
 if [ -x $MP ] && [ -x $MPS ]; then
   # the reference against itself first (its scalar and AVX2 builds, CPU only): the spread two correct evaluations of this model have
-  timeout -k 10 600 $MPS --preset 8b --layers 32 --vocab 128256 --tokens 4 --dump /tmp/m8b_scalar.bin > gpurun_out/m8b_dump_scalar.log 2>&1 || exit 1
-  timeout -k 10 300 $MP  --preset 8b --layers 32 --vocab 128256 --tokens 4 --dump /tmp/m8b_avx2.bin   > gpurun_out/m8b_dump_avx2.log 2>&1 || exit 1
+  timeout -k 10 600 $MPS --preset 8b --layers 32 --vocab 128256 --tokens 4 --dump /tmp/m8b_scalar.bin > $OUT/m8b_dump_scalar.log 2>&1 || exit 1
+  timeout -k 10 300 $MP  --preset 8b --layers 32 --vocab 128256 --tokens 4 --dump /tmp/m8b_avx2.bin   > $OUT/m8b_dump_avx2.log 2>&1 || exit 1
   {
     echo "# $TAG: Llama-3-8B-shaped model (32 layers, 128256-row output, random Q4_K_M weights) through ggml_backend_graph_compute of libggml-mi355.so"
     echo; echo "Harness: oracle/model_parity (reference libggml host side). Logits of the plugin against the reference CPU backend (AVX2 build), each step"
@@ -86,7 +87,7 @@ if [ -f llama.cpp.dsp_amd/lib/libmi355q_dbg.so ]; then
   tail -8 profiles/${TAG}_plan_timeline.md | cut -c1-200
 fi
 step "prefill shapes"
-timeout -k 10 300 python tools/ppbench.py > gpurun_out/ppbench.log 2>&1; rc=$?; tail -9 gpurun_out/ppbench.log; [ $rc -ne 0 ] && exit $rc
-cp gpurun_out/ppbench.log profiles/${TAG}_ppbench.txt
-cp profiles/${TAG}_* gpurun_out/
+timeout -k 10 300 python tools/ppbench.py > $OUT/ppbench.log 2>&1; rc=$?; tail -9 $OUT/ppbench.log; [ $rc -ne 0 ] && exit $rc
+cp $OUT/ppbench.log profiles/${TAG}_ppbench.txt
+cp profiles/${TAG}_* $OUT/
 exit 0
