@@ -298,19 +298,22 @@ int     mi355q_plan_destroy(mi355q_plan *plan);
 
 /* ---- residency ops: the small f32/f16 graph ops between the quantized matmuls of a decode graph ------
  * Tensors are described the ggml way: ne[] elements per dimension, nb[] strides in BYTES (views, permutes and broadcasts
- * are expressed through them), data = device pointer.  type: MI355Q_T_F32 / MI355Q_T_F16.  Each function is the device
+ * are expressed through them), data = device pointer.  type: MI355Q_T_F32 / MI355Q_T_F16, and MI355Q_T_BF16 (ggml's id 30, a bf16 KV cache)
+ * where an op says so; f32 -> bf16 is the CPU's ggml_compute_fp32_to_bf16 (round to nearest even, NaN -> (bits >> 16) | 0x40).  Each function is the device
  * counterpart of one ggml CPU op and follows its arithmetic (cited in csrc/ops_glue.hip):
  *   op_bin_bcast  GGML_OP_ADD/SUB/MUL/DIV   dst = a (op) b, b broadcast over a (ne_a % ne_b == 0), dst has a's shape
  *   op_unary      GGML_OP_UNARY             SILU, RELU, SIGMOID, TANH, NEG, ABS
  *   op_rms_norm   GGML_OP_RMS_NORM          per row: x / sqrt(mean(x^2) + eps), f32, rows contiguous
- *   op_cpy        GGML_OP_CPY/CONT/DUP      logical element order, any strides, f32 <-> f16
+ *   op_cpy        GGML_OP_CPY/CONT/DUP      logical element order, any strides, among f32 / f16 / bf16
  *   op_soft_max   GGML_OP_SOFT_MAX          softmax(a*scale + slope*mask) per row; mask f32/f16 [ne00, >= ne01] or NULL
  *   op_rope       GGML_OP_ROPE              normal (mode 0) and neox (mode 2) rotary embedding, YaRN parameters, optional
  *                                           frequency factors (src2); pos = i32 device [ne2]
- *   op_mul_mat_f  GGML_OP_MUL_MAT           with an f16 or f32 src0 (attention KQ / KQV): dst[m,n] = sum_k a[k,m] b[k,n],
- *                                           dims 2/3 of src0 broadcast; an f16 src0 rounds src1 to f16 as the CPU does          */
+ *   op_mul_mat_f  GGML_OP_MUL_MAT           with an f16, bf16 or f32 src0 (attention KQ / KQV): dst[m,n] = sum_k a[k,m] b[k,n],
+ *                                           dims 2/3 of src0 broadcast; an f16 / bf16 src0 rounds src1 to f16 / bf16 as the CPU does
+ *   op_get_rows   GGML_OP_GET_ROWS          f32 / f16 / bf16 rows -> f32                                                          */
 #define MI355Q_T_F32 0
 #define MI355Q_T_F16 1
+#define MI355Q_T_BF16 30
 typedef struct mi355q_tensor {
     void   *data;
     int     type;
@@ -341,6 +344,8 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
 /* GGML_OP_FLASH_ATTN_EXT (ggml.c ggml_flash_attn_ext; CPU ggml-cpu/ops.cpp:6690-6905) for an f16 KV cache:
  *   q f32 [DK, N, H, B], k f16 [DK, n_kv, Hk, Bk], v f16 [DV, n_kv, Hv, Bv] (NOT transposed), mask f16 [>= n_kv, >= N] or NULL,
  *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256, n_kv <= 36864.
+ * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
+ * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types are not accepted.
  * workspace (optional, mi355q_op_flash_attn_ext_workspace bytes): with it, a call with few query rows (decode) splits the KV range over
  * several workgroups per row and merges the pieces in a second launch, and a call with >= 16 query rows (prefill) computes scores,
  * softmax and P V on the matrix-core kernels with the scores of the batch in the workspace; without it every row is one workgroup.   */

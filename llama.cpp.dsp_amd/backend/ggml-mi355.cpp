@@ -8,10 +8,11 @@
 //
 // Scope: the quantized MUL_MAT / MUL_MAT_ID hot path and, so that a decode graph stays resident on the
 // device, the f32 / f16 ops between those matmuls.  supports_op is true for
-//   * GGML_OP_MUL_MAT    with quantized src0 (the 19 types of mi355q_type_supported) or f16 / f32 src0, f32 src1, f32 dst
+//   * GGML_OP_MUL_MAT    with quantized src0 (the 19 types of mi355q_type_supported) or f16 / bf16 / f32 src0, f32 src1, f32 dst
 //   * GGML_OP_MUL_MAT_ID with the same quantized src0 types (expert ids stay on the device)
-//   * ADD SUB MUL DIV SCALE, UNARY (SILU RELU SIGMOID TANH NEG ABS), RMS_NORM, CPY CONT DUP (f32 <-> f16), GET_ROWS, SOFT_MAX, ROPE,
-//     FLASH_ATTN_EXT (f16 K / V), ARGSORT, SUM_ROWS -- the variants a llama / mixtral graph uses (mi355_supports_op lists them)
+//   * ADD SUB MUL DIV SCALE, UNARY (SILU RELU SIGMOID TANH NEG ABS), RMS_NORM, CPY CONT DUP (among f32 / f16 / bf16; f32 -> q8_0 / q4_0),
+//     GET_ROWS (f32 / f16 / bf16 rows), SOFT_MAX, ROPE, FLASH_ATTN_EXT (f16, bf16, q8_0 or q4_0 K / V), ARGSORT, SUM_ROWS -- the variants
+//     a llama / mixtral graph uses (mi355_supports_op lists them); so -ctk / -ctv f16, bf16, q8_0 and q4_0 caches stay resident
 //   * the no-op view ops NONE / RESHAPE / VIEW / PERMUTE / TRANSPOSE on our own buffers
 // everything else stays on the CPU backend.  The fork's own DSP backend (ggml/src/ggml-dsp/ggml-dsp.cpp)
 // is the structural template for where each hook goes; none of its code is reused.
@@ -373,11 +374,21 @@ static void mi355_backend_synchronize(ggml_backend_t backend) {
 // ---- residency ops: thin wrappers over mi355q_op_* -- the tensor descriptor is ggml's ne[] / nb[] verbatim
 static mi355q_tensor mi355_td(const struct ggml_tensor * t) {
     mi355q_tensor d;
-    d.data = t->data; d.type = t->type == GGML_TYPE_F16 ? MI355Q_T_F16 : t->type == GGML_TYPE_Q8_0 ? MI355Q_TYPE_Q8_0 : t->type == GGML_TYPE_Q4_0 ? MI355Q_TYPE_Q4_0 : MI355Q_T_F32;     // (Q8_0: a quantized KV cache, CPY destination / FLASH_ATTN_EXT operand)
+    d.data = t->data;
+    switch (t->type) {
+    case GGML_TYPE_F32:  d.type = MI355Q_T_F32;     break;
+    case GGML_TYPE_I32:  d.type = MI355Q_T_F32;     break;     // (row ids of GET_ROWS: 4-byte elements, read as int32 by the op)
+    case GGML_TYPE_F16:  d.type = MI355Q_T_F16;     break;
+    case GGML_TYPE_BF16: d.type = MI355Q_T_BF16;    break;     // (a bf16 KV cache, a bf16 embedding table)
+    case GGML_TYPE_Q8_0: d.type = MI355Q_TYPE_Q8_0; break;     // (Q8_0 / Q4_0: a quantized KV cache, CPY destination / FLASH_ATTN_EXT operand)
+    case GGML_TYPE_Q4_0: d.type = MI355Q_TYPE_Q4_0; break;
+    default: GGML_ABORT("mi355_td: tensor type %s has no residency-op form", ggml_type_name(t->type));
+    }
     for (int i = 0; i < 4; ++i) { d.ne[i] = t->ne[i]; d.nb[i] = (int64_t) t->nb[i]; }
     return d;
 }
 static bool mi355_f32_or_f16(enum ggml_type t) { return t == GGML_TYPE_F32 || t == GGML_TYPE_F16; }
+static bool mi355_float_type(enum ggml_type t) { return t == GGML_TYPE_F32 || t == GGML_TYPE_F16 || t == GGML_TYPE_BF16; }
 
 static int mi355_unary_code(enum ggml_unary_op u) {
     switch (u) {
@@ -452,7 +463,7 @@ static void mi355_glue_op(mi355_backend_ctx * ctx, struct ggml_tensor * dst, int
         memcpy(&p.attn_factor, q + 8, 4); memcpy(&p.beta_fast, q + 9, 4); memcpy(&p.beta_slow, q + 10, 4);
         MQ_CHECK(mi355q_op_rope(&a, (const int32_t *) dst->src[1]->data, dst->src[2] ? (const float *) dst->src[2]->data : nullptr, &d, &p, ctx->stream));
     } break;
-    case GGML_OP_MUL_MAT: {                                   // f16 / f32 src0 (the quantized types go through mi355_mul_mat)
+    case GGML_OP_MUL_MAT: {                                   // f16 / bf16 / f32 src0 (the quantized types go through mi355_mul_mat)
         const mi355q_tensor b = mi355_td(dst->src[1]);
         MQ_CHECK(mi355q_op_mul_mat_f(&a, &b, &d, ctx->stream));
     } break;
@@ -980,7 +991,7 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
     case GGML_OP_MUL_MAT: {
         const struct ggml_tensor * a = op->src[0];
         const struct ggml_tensor * b = op->src[1];
-        if (mi355_f32_or_f16(a->type)) {                          // attention KQ / KQV: k contiguous in both operands, any other strides
+        if (mi355_float_type(a->type)) {                          // attention KQ / KQV (f16 / bf16 cache): k contiguous in both operands, any other strides
             if (b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !mi355_operand_ok(a) || !mi355_operand_ok(b)) return false;
             return a->nb[0] == ggml_type_size(a->type) && b->nb[0] == sizeof(float) && (op->ne[0] * op->ne[1] * op->ne[2] * op->ne[3] + 3) / 4 <= 0x7FFFFFFF;
         }
@@ -1029,12 +1040,12 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         if (op->op == GGML_OP_CPY && (op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q4_0))      // the K / V stores of a quantized cache (-ctk q8_0 / q4_0): whole blocks, contiguous destination
             return a->type == GGML_TYPE_F32 && mi355_operand_ok(a) && a->nb[0] == sizeof(float) && a->ne[0] % 32 == 0 && op->ne[0] % 32 == 0 &&
                    ggml_is_contiguous(op) && ggml_nelements(a) == ggml_nelements(op) && mi355_q80_canonical(op);
-        return mi355_f32_or_f16(a->type) && mi355_f32_or_f16(op->type) && mi355_operand_ok(a) && ggml_nelements(a) == ggml_nelements(op);
+        return mi355_float_type(a->type) && mi355_float_type(op->type) && mi355_operand_ok(a) && ggml_nelements(a) == ggml_nelements(op);
     }
     case GGML_OP_GET_ROWS: {
         const struct ggml_tensor * a = op->src[0];
         const struct ggml_tensor * ids = op->src[1];
-        return mi355_f32_or_f16(a->type) && op->type == GGML_TYPE_F32 && ids->type == GGML_TYPE_I32 && mi355_operand_ok(a) && mi355_operand_ok(ids);
+        return mi355_float_type(a->type) && op->type == GGML_TYPE_F32 && ids->type == GGML_TYPE_I32 && mi355_operand_ok(a) && mi355_operand_ok(ids);
     }
     case GGML_OP_SCALE: {
         const struct ggml_tensor * a = op->src[0];
@@ -1056,11 +1067,13 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         if (op->src[2] && op->src[2]->type != GGML_TYPE_F32) return false;
         return a->ne[0] % 2 == 0;
     }
-    case GGML_OP_FLASH_ATTN_EXT: {                            // f16 or Q8_0 KV cache, f32 queries, f16 mask; other cache types stay on the CPU
+    case GGML_OP_FLASH_ATTN_EXT: {                            // f16, bf16, Q8_0 or Q4_0 KV cache, f32 queries, f16 mask; other cache types stay on the CPU
         const struct ggml_tensor * q = op->src[0], * k = op->src[1], * v = op->src[2], * m = op->src[3];
         const bool kv_q80 = (k->type == GGML_TYPE_Q8_0 && v->type == GGML_TYPE_Q8_0) || (k->type == GGML_TYPE_Q4_0 && v->type == GGML_TYPE_Q4_0);       // a Q8_0 / Q4_0 cache: the one-workgroup-per-row kernel with the CPU's arithmetic
+        const bool kv_bf16 = k->type == GGML_TYPE_BF16 && v->type == GGML_TYPE_BF16;          // a bf16 cache: the same kernel's bf16 form, or the matrix cores for a batch
         const size_t kv_bb = k->type == GGML_TYPE_Q4_0 ? 18u : 34u;
-        if (q->type != GGML_TYPE_F32 || !((k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16) || kv_q80) || op->type != GGML_TYPE_F32) return false;
+        if (q->type != GGML_TYPE_F32 || !((k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16) || kv_q80 || kv_bf16) || op->type != GGML_TYPE_F32) return false;
+        if (kv_bf16 && k->ne[1] > 8192) return false;
         if (!mi355_operand_ok(q) || !mi355_operand_ok(k) || !mi355_operand_ok(v) || (m && !mi355_operand_ok(m))) return false;
         if (q->nb[0] != 4 || k->nb[0] != (kv_q80 ? kv_bb : 2u) || v->nb[0] != (kv_q80 ? kv_bb : 2u) || !ggml_is_contiguous(op)) return false;
         if (kv_q80 && (k->ne[0] % 32 || v->ne[0] % 32 || k->ne[1] > 8192 || !mi355_q80_canonical(k) || !mi355_q80_canonical(v))) return false;

@@ -12,6 +12,8 @@
 //   ROPE                    ggml-cpu/ops.cpp:4990-5270 (normal / neox, YaRN, frequency factors)
 //   GET_ROWS, SCALE         ggml-cpu/ops.cpp:4272-4311, 3840-3878
 //   MUL_MAT f16/f32 x f32   ggml-cpu.c:1266-1458 with vec_dot_type F16 / F32 (attention KQ, KQV)
+//   bf16 (a bf16 KV cache)  CPY / GET_ROWS / MUL_MAT / FLASH_ATTN_EXT with bf16 operands: f32 -> bf16 is ggml_compute_fp32_to_bf16 (ggml-impl.h),
+//                           dot products ggml_vec_dot_bf16 in its AVX2 order (ggml-cpu/vec.cpp) -- DESIGN.md section 5.7d
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -20,7 +22,7 @@
 
 namespace mi355q {
 
-struct TensorD { char * data; int type; int64_t ne[4]; int64_t nb[4]; };     // device copy of mi355q_tensor (type: 0 f32, 1 f16)
+struct TensorD { char * data; int type; int64_t ne[4]; int64_t nb[4]; };     // device copy of mi355q_tensor (type: 0 f32, 1 f16, 30 bf16)
 
 static TensorD to_d(const mi355q_tensor * t) {
     TensorD d; d.data = (char *) t->data; d.type = t->type;
@@ -32,11 +34,24 @@ static bool same_shape(const mi355q_tensor * a, const mi355q_tensor * b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];
 }
 
+// f32 -> bf16 as the CPU does it (ggml_compute_fp32_to_bf16, ggml-impl.h): round to nearest even on the bits, subnormals kept, a NaN made quiet
+// as (bits >> 16) | 0x40.  (The hardware v_cvt_pk_bf16_f32 keeps other NaN bits; the integer form is the contract.)  bf16 -> f32 is exact.
+__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t) ((u >> 16) | 0x40u);
+    return (uint16_t) ((u + (0x7FFFu + ((u >> 16) & 1u))) >> 16);
+}
+__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t) h << 16); }
+__device__ __forceinline__ float bf16_round(float f) { return bf16_to_f32(f32_to_bf16(f)); }
+
 __device__ __forceinline__ float ld_elem(const char * p, int type) {
-    return type == 0 ? *(const float *) p : __half2float(*(const __half *) p);
+    return type == 0 ? *(const float *) p : type == MI355Q_T_BF16 ? bf16_to_f32(*(const uint16_t *) p) : __half2float(*(const __half *) p);
+}
+__device__ __forceinline__ uint16_t to_16(float v, int type) {                  // f32 -> the bits of a 16-bit element of `type` (f16 or bf16)
+    return type == MI355Q_T_BF16 ? f32_to_bf16(v) : __half_as_ushort(__float2half_rn(v));
 }
 __device__ __forceinline__ void st_elem(char * p, int type, float v) {
-    if (type == 0) *(float *) p = v; else *(__half *) p = __float2half_rn(v);
+    if (type == 0) *(float *) p = v; else *(uint16_t *) p = to_16(v, type);
 }
 
 // ---- binary ops with ggml broadcasting: dst[i] = a[i] (op) b[i % ne_b] ------------------------------
@@ -196,7 +211,7 @@ __global__ void __launch_bounds__(256) k_unary_mul(const float * __restrict__ a,
     }
 }
 
-// ---- CPY / CONT / DUP: logical element order, any strides, f32 <-> f16 -------------------------------------
+// ---- CPY / CONT / DUP: logical element order, any strides, f32 / f16 / bf16 (a conversion goes through f32, as ggml_compute_forward_dup does) --
 __global__ void __launch_bounds__(256) k_cpy(const TensorD a, TensorD d, int64_t n, char * const * dest_table, int dest_index) {
     if (dest_table) d.data = dest_table[dest_index];           // destination resolved on the device (graph replay with a moving KV position)
     for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t) gridDim.x * blockDim.x) {
@@ -229,17 +244,17 @@ __global__ void __launch_bounds__(256) k_cpy_rows4(const TensorD a, TensorD d, i
             if (((uintptr_t) src & 15) == 0) { const float4 t = *(const float4 *) src; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
             else { for (int j = 0; j < 4; ++j) v[j] = ((const float *) src)[j]; }
         } else {
-            for (int j = 0; j < 4; ++j) v[j] = __half2float(((const __half *) src)[j]);
+            for (int j = 0; j < 4; ++j) v[j] = ld_elem(src + 2 * j, a.type);
         }
         if (d.type == 0) {
             if (((uintptr_t) dst & 15) == 0) *(float4 *) dst = make_float4(v[0], v[1], v[2], v[3]);
             else { for (int j = 0; j < 4; ++j) ((float *) dst)[j] = v[j]; }
         } else {
-            __half h[4];
-            if (a.type == 1) { for (int j = 0; j < 4; ++j) h[j] = ((const __half *) src)[j]; }
-            else             { for (int j = 0; j < 4; ++j) h[j] = __float2half_rn(v[j]); }
+            uint16_t h[4];
+            if (a.type == d.type) { for (int j = 0; j < 4; ++j) h[j] = ((const uint16_t *) src)[j]; }
+            else                  { for (int j = 0; j < 4; ++j) h[j] = to_16(v[j], d.type); }
             if (((uintptr_t) dst & 7) == 0) *(uint2 *) dst = *(const uint2 *) h;
-            else { for (int j = 0; j < 4; ++j) ((__half *) dst)[j] = h[j]; }
+            else { for (int j = 0; j < 4; ++j) ((uint16_t *) dst)[j] = h[j]; }
         }
     }
 }
@@ -247,17 +262,22 @@ __global__ void __launch_bounds__(256) k_cpy_transpose(const TensorD a, TensorD 
     if (dest_table) d.data = dest_table[dest_index];
     __shared__ float tile[32][33];                              // 32 x 32 tiles: a 512 x 1024 V store is 512 workgroups, not 128
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const bool raw = a.type == MI355Q_T_BF16 && d.type == MI355Q_T_BF16;
     const int64_t b0 = (int64_t) blockIdx.x * 32, b1 = (int64_t) blockIdx.y * 32, i2 = blockIdx.z % a.ne[2], i3 = blockIdx.z / a.ne[2];
     const char * ab = a.data + i2 * a.nb[2] + i3 * a.nb[3];
     char * db = d.data + i2 * d.nb[2] + i3 * d.nb[3];
     for (int j = ty; j < 32; j += 8) {                           // read: lanes run along the source's contiguous dim 1
         const int64_t i0 = b0 + j, i1 = b1 + tx;
-        if (i0 < a.ne[0] && i1 < a.ne[1]) tile[j][tx] = ld_elem(ab + i0 * a.nb[0] + i1 * a.nb[1], a.type);
+        // (bf16 -> bf16 moves the bits: the f32 round trip would quieten a signalling NaN, the CPU's copy does not)
+        if (i0 < a.ne[0] && i1 < a.ne[1]) tile[j][tx] = raw ? __uint_as_float(*(const uint16_t *) (ab + i0 * a.nb[0] + i1 * a.nb[1])) : ld_elem(ab + i0 * a.nb[0] + i1 * a.nb[1], a.type);
     }
     __syncthreads();
     for (int j = ty; j < 32; j += 8) {                           // write: lanes run along the destination's contiguous dim 0
         const int64_t i0 = b0 + tx, i1 = b1 + j;
-        if (i0 < a.ne[0] && i1 < a.ne[1]) st_elem(db + i0 * d.nb[0] + i1 * d.nb[1], d.type, tile[tx][j]);
+        if (i0 < a.ne[0] && i1 < a.ne[1]) {
+            char * p = db + i0 * d.nb[0] + i1 * d.nb[1];
+            if (raw) *(uint16_t *) p = (uint16_t) __float_as_uint(tile[tx][j]); else st_elem(p, d.type, tile[tx][j]);
+        }
     }
 }
 static int grid_for(int64_t n);
@@ -501,6 +521,39 @@ __global__ void __launch_bounds__(256) k_mul_mat_f(const TensorD a, const Tensor
     const char * abase = a.data + i02 * a.nb[2] + i03 * a.nb[3];
     const float * bp = (const float *) (b.data + n * b.nb[1] + i12 * b.nb[2] + i13 * b.nb[3]);
     const int64_t K = a.ne[0];
+    if (a.type == MI355Q_T_BF16) {
+        // ggml_vec_dot_bf16 with src1 rounded to bf16 first (vec_dot_type BF16), AVX2 branch (vec.cpp): element i of every 32-element chunk goes
+        // to accumulator (i % 32) / 8, lane i % 8, by a multiply then an add; the tree (c1 + c3) + (c2 + c4), high half + low half, movehl,
+        // movehdup; the K % 32 tail is added in double one f32 product at a time.  Lane l of half h owns accumulator element l of rows
+        // m0 + 4 h .. m0 + 4 h + 3: the shuffles below are that tree.
+        const int h = lane >> 5, l = lane & 31;
+        const int64_t K32 = K & ~(int64_t) 31;
+        const char * ar[MMF_ROWS / 2];
+        float c[MMF_ROWS / 2];
+#pragma unroll
+        for (int q = 0; q < MMF_ROWS / 2; ++q) { const int64_t m = m0 + 4 * h + q; ar[q] = abase + (m < M ? m : m0) * a.nb[1]; c[q] = 0.0f; }
+        for (int64_t k0 = 0; k0 < K32; k0 += 32) {
+            const float bv = bf16_round(bp[k0 + l]);
+#pragma unroll
+            for (int q = 0; q < MMF_ROWS / 2; ++q) c[q] = __fadd_rn(__fmul_rn(bf16_to_f32(((const uint16_t *) ar[q])[k0 + l]), bv), c[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < MMF_ROWS / 2; ++q) {
+            float x = c[q];
+            x = __fadd_rn(x, __shfl_xor(x, 16, 64));             // c1 + c3 | c2 + c4
+            x = __fadd_rn(x, __shfl_xor(x, 8, 64));              // (c1 + c3) + (c2 + c4), lane l % 8
+            x = __fadd_rn(x, __shfl_xor(x, 4, 64));              // high half + low half
+            x = __fadd_rn(x, __shfl_xor(x, 2, 64));              // movehl
+            x = __fadd_rn(x, __shfl_xor(x, 1, 64));              // movehdup
+            const int64_t m = m0 + 4 * h + q;
+            if (l == 0 && m < M) {
+                double sum = (double) x;
+                for (int64_t k = K32; k < K; ++k) sum += (double) __fmul_rn(bf16_to_f32(((const uint16_t *) ar[q])[k]), bf16_round(bp[k]));
+                *(float *) (d.data + m * d.nb[0] + n * d.nb[1] + i12 * d.nb[2] + i13 * d.nb[3]) = (float) sum;
+            }
+        }
+        return;
+    }
     float s[MMF_ROWS];
 #pragma unroll
     for (int q = 0; q < MMF_ROWS; ++q) s[q] = 0.0f;
@@ -689,11 +742,13 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
 // ggml_vec_dot_q8_0_q8_0 in its AVX2 order (per block d = d_k * d_q, eight f32 lane sums of four int8 products each fed by fma, hsum tree), the online
 // softmax walked in order (prefix maximum, as in k_flash_attn_ext's seq mode), V dequantized (q * d) into an F32 accumulator: scale by f32 multiply when
 // the maximum grows, v * weight by f32 fma per position (ggml_vec_scale_f32 / ggml_vec_mad_f32).
-template <int KVT>                                                          // MI355Q_TYPE_Q8_0 (34-byte blocks) or MI355Q_TYPE_Q4_0 (18-byte blocks: f16 d, 16 bytes of nibbles, low = elements 0..15)
+// KVT = MI355Q_T_BF16 (a bf16 cache): q rounded to bf16 (ggml_compute_fp32_to_bf16), scores by ggml_vec_dot_bf16 in its AVX2 order (see
+// k_mul_mat_f; any head size: the tail past the last 32-chunk in double), V widened exactly to f32; the softmax walk and the F32 accumulator as above.
+template <int KVT>                                                          // MI355Q_TYPE_Q8_0 (34-byte blocks), MI355Q_TYPE_Q4_0 (18-byte blocks: f16 d, 16 bytes of nibbles, low = elements 0..15) or MI355Q_T_BF16
 __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD q, const TensorD k, const TensorD v, const TensorD m, int has_mask, const TensorD d,
                                                                    float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2) {
-    extern __shared__ __attribute__((aligned(16))) float fq_s[];             // [n_kv] scores -> weights | [n_kv] rescale factors | q: [DK / 32] block scales, [DK / 4] packed quants
-    constexpr int BB = KVT == MI355Q_TYPE_Q8_0 ? 34 : 18;                      // bytes per 32-element block of the cache
+    extern __shared__ __attribute__((aligned(16))) float fq_s[];             // [n_kv] scores -> weights | [n_kv] rescale factors | q: [DK / 32] block scales, [DK / 4] packed quants (bf16: [DK] rounded values)
+    constexpr int BB = KVT == MI355Q_TYPE_Q8_0 ? 34 : 18;                      // bytes per 32-element block of the cache (not used for bf16)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t t = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int64_t DK = k.ne[0], DV = v.ne[0], n_kv = k.ne[1];
@@ -702,8 +757,10 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     uint32_t * qq = (uint32_t *) (qd + (DK >> 5));
     const float slope = max_bias > 0.0f ? ((uint32_t) h < n_head_log2 ? powf(m0, (float) (h + 1)) : powf(m1, (float) (2 * (h - n_head_log2) + 1))) : 1.0f;
     const __half * mp = has_mask ? (const __half *) (m.data + t * m.nb[1]) : nullptr;
-    // ---- q -> Q8_0 (whole waves take part: the 8-lane reductions)
-    if (tid < ((DK / 4 + 63) & ~63)) {
+    // ---- q -> Q8_0 (whole waves take part: the 8-lane reductions); q -> bf16
+    if constexpr (KVT == MI355Q_T_BF16) {
+        if (tid < DK) qd[tid] = bf16_round(((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]))[tid]);
+    } else if (tid < ((DK / 4 + 63) & ~63)) {
         const float * qp = (const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]);
         const int e = 4 * tid;
         const float4 x = e < DK ? make_float4(qp[e], qp[e + 1], qp[e + 2], qp[e + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -717,7 +774,30 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     for (int64_t j = tid; j < n_kv; j += FA_THREADS) {
         const float mv = mp ? __fmul_rn(slope, __half2float(mp[j])) : 0.0f;
         float s = -INFINITY;
-        if (mv != -INFINITY) {                                                // (a masked position is skipped by the CPU whatever its cache row holds)
+        if (mv != -INFINITY && KVT == MI355Q_T_BF16) {
+            const char * row = k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3];
+            const bool al = (((uintptr_t) row) & 15) == 0;
+            float c[32];                                                      // accumulator (i % 32) / 8, lane i % 8 at c[i % 32]
+#pragma unroll
+            for (int i = 0; i < 32; ++i) c[i] = 0.0f;
+            for (int blk = 0; blk < nblk; ++blk) {
+                uint16_t kb[32];
+                if (al) { for (int u = 0; u < 4; ++u) *(uint4 *) (kb + 8 * u) = ((const uint4 *) (row + 64 * blk))[u]; }
+                else    { for (int i = 0; i < 32; ++i) kb[i] = ((const uint16_t *) (row + 64 * blk))[i]; }
+#pragma unroll
+                for (int i = 0; i < 32; ++i) c[i] = __fadd_rn(__fmul_rn(bf16_to_f32(kb[i]), qd[32 * blk + i]), c[i]);
+            }
+            float u8[8];
+#pragma unroll
+            for (int l = 0; l < 8; ++l) u8[l] = __fadd_rn(__fadd_rn(c[l], c[16 + l]), __fadd_rn(c[8 + l], c[24 + l]));     // (c1 + c3) + (c2 + c4)
+            const float g0 = __fadd_rn(u8[4], u8[0]), g1 = __fadd_rn(u8[5], u8[1]), g2 = __fadd_rn(u8[6], u8[2]), g3 = __fadd_rn(u8[7], u8[3]);
+            double sum = (double) __fadd_rn(__fadd_rn(g0, g2), __fadd_rn(g1, g3));
+            for (int64_t i = 32 * (int64_t) nblk; i < DK; ++i) sum += (double) __fmul_rn(bf16_to_f32(((const uint16_t *) row)[i]), qd[i]);
+            s = (float) sum;
+            s = __fmul_rn(s, scale);
+            if (softcap != 0.0f) s = softcap * tanhf(s);
+            s = __fadd_rn(s, mv);
+        } else if (mv != -INFINITY) {                                         // (a masked position is skipped by the CPU whatever its cache row holds)
             const char * row = k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3];
             float acc[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
             for (int blk = 0; blk < nblk; ++blk) {
@@ -769,7 +849,21 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     }
     __syncthreads();
     // ---- V . P in an F32 accumulator, a thread per output dim
-    if (tid < DV) {
+    if (KVT == MI355Q_T_BF16 && tid < DV) {
+        const char * vb = v.data + hv * v.nb[2] + bv * v.nb[3] + 2 * (int64_t) tid;
+        float acc = 0.0f, S = 0.0f;
+#pragma unroll 4
+        for (int64_t j = 0; j < n_kv; ++j) {
+            const float vs = fq_s[j], ms = msv[j];
+            if (vs != 0.0f || ms != 1.0f) {                                   // (uniform)
+                const float vv = bf16_to_f32(*(const uint16_t *) (vb + j * v.nb[1]));
+                if (ms != 1.0f) acc = __fmul_rn(acc, ms);                     // ggml_vec_scale_f32
+                acc = __builtin_fmaf(vv, vs, acc);                            // ggml_vec_mad_f32 (its scalar leftovers are contracted to fma too)
+                S = __fadd_rn(__fmul_rn(S, ms), vs);
+            }
+        }
+        *(float *) (d.data + tid * d.nb[0] + h * d.nb[1] + t * d.nb[2] + b * d.nb[3]) = __fmul_rn(acc, __fdiv_rn(1.0f, S));
+    } else if (KVT != MI355Q_T_BF16 && tid < DV) {
         const char * vb = v.data + hv * v.nb[2] + bv * v.nb[3] + BB * (tid >> 5);
         const int e = tid & 31;
         float acc = 0.0f, S = 0.0f;
@@ -833,7 +927,10 @@ typedef float    mmf_f4 __attribute__((ext_vector_type(4)));
 constexpr int MMF_T = 64, MMF_K = 64, MMF_LDS_ROW = MMF_K * 2 + 16;
 // AT: src0 is given TRANSPOSED in memory -- a.data[k][m] with m contiguous (a.nb[1] = bytes between consecutive k): the V cache of the
 // flash-attention layout, one row per position, read for out[n][m] = sum_k p[n][k] v[k][m].  a.ne still reads [K, M, ..].
-template <bool AT>
+// BF: src0 bf16 (a bf16 KV cache) -- the same tiles on v_mfma_f32_16x16x32_bf16 (its A / B lane maps are those of the f16 form), src1 rounded to
+// bf16 by the CPU's rule (f32_to_bf16) on the way into LDS.  Products of two bf16 numbers are exact in f32: again only the summation order differs.
+typedef __bf16   mmf_b8 __attribute__((ext_vector_type(8)));
+template <bool AT, bool BF = false>
 __global__ void __launch_bounds__(256) k_mul_mat_f16_mfma(const TensorD a, const TensorD b, const TensorD d) {
     __shared__ __attribute__((aligned(16))) uint8_t As[MMF_T * MMF_LDS_ROW], Bs[MMF_T * MMF_LDS_ROW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
@@ -881,23 +978,41 @@ __global__ void __launch_bounds__(256) k_mul_mat_f16_mfma(const TensorD a, const
         } else {
             *(uint4 *) (As + row * MMF_LDS_ROW + 32 * seg) = a0; *(uint4 *) (As + row * MMF_LDS_ROW + 32 * seg + 16) = a1;
         }
-        const mmf_h8 h0 = { (_Float16) f0.x, (_Float16) f0.y, (_Float16) f0.z, (_Float16) f0.w, (_Float16) f1.x, (_Float16) f1.y, (_Float16) f1.z, (_Float16) f1.w };
-        const mmf_h8 h1 = { (_Float16) f2.x, (_Float16) f2.y, (_Float16) f2.z, (_Float16) f2.w, (_Float16) f3.x, (_Float16) f3.y, (_Float16) f3.z, (_Float16) f3.w };
-        *(mmf_h8 *) (Bs + row * MMF_LDS_ROW + 32 * seg) = h0; *(mmf_h8 *) (Bs + row * MMF_LDS_ROW + 32 * seg + 16) = h1;
+        if constexpr (BF) {
+            auto pk = [](float x, float y) { return (uint32_t) f32_to_bf16(x) | ((uint32_t) f32_to_bf16(y) << 16); };
+            *(uint4 *) (Bs + row * MMF_LDS_ROW + 32 * seg)      = make_uint4(pk(f0.x, f0.y), pk(f0.z, f0.w), pk(f1.x, f1.y), pk(f1.z, f1.w));
+            *(uint4 *) (Bs + row * MMF_LDS_ROW + 32 * seg + 16) = make_uint4(pk(f2.x, f2.y), pk(f2.z, f2.w), pk(f3.x, f3.y), pk(f3.z, f3.w));
+        } else {
+            const mmf_h8 h0 = { (_Float16) f0.x, (_Float16) f0.y, (_Float16) f0.z, (_Float16) f0.w, (_Float16) f1.x, (_Float16) f1.y, (_Float16) f1.z, (_Float16) f1.w };
+            const mmf_h8 h1 = { (_Float16) f2.x, (_Float16) f2.y, (_Float16) f2.z, (_Float16) f2.w, (_Float16) f3.x, (_Float16) f3.y, (_Float16) f3.z, (_Float16) f3.w };
+            *(mmf_h8 *) (Bs + row * MMF_LDS_ROW + 32 * seg) = h0; *(mmf_h8 *) (Bs + row * MMF_LDS_ROW + 32 * seg + 16) = h1;
+        }
         __syncthreads();
         if (k0 + MMF_K < K) fetch(k0 + MMF_K);
 #pragma unroll
         for (int kk = 0; kk < MMF_K / 32; ++kk) {
             const int koff = 2 * (32 * kk + 8 * (lane >> 4));
-            mmf_h8 af[2], bf[2];
+            if constexpr (BF) {
+                mmf_b8 af[2], bf[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) af[i] = *(const mmf_h8 *) (As + (32 * wm + 16 * i + (lane & 15)) * MMF_LDS_ROW + koff);
+                for (int i = 0; i < 2; ++i) af[i] = *(const mmf_b8 *) (As + (32 * wm + 16 * i + (lane & 15)) * MMF_LDS_ROW + koff);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = *(const mmf_h8 *) (Bs + (32 * wn + 16 * j + (lane & 15)) * MMF_LDS_ROW + koff);
+                for (int j = 0; j < 2; ++j) bf[j] = *(const mmf_b8 *) (Bs + (32 * wn + 16 * j + (lane & 15)) * MMF_LDS_ROW + koff);
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+            } else {
+                mmf_h8 af[2], bf[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) af[i] = *(const mmf_h8 *) (As + (32 * wm + 16 * i + (lane & 15)) * MMF_LDS_ROW + koff);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bf[j] = *(const mmf_h8 *) (Bs + (32 * wn + 16 * j + (lane & 15)) * MMF_LDS_ROW + koff);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
+            }
         }
     }
     // C rows = src0 rows m (4 consecutive per lane), C column = src1 row n
@@ -1078,13 +1193,15 @@ static int cpy_to_q8_0(const mi355q_tensor * a, const mi355q_tensor * dst, char 
     return MI355Q_OK;
 }
 
+static bool cpy_type(int t) { return t == MI355Q_T_F32 || t == MI355Q_T_F16 || t == MI355Q_T_BF16; }
+
 int mi355q_op_cpy(const mi355q_tensor * a, const mi355q_tensor * dst, void * stream) {
     if (!a || !dst || nelements(a) != nelements(dst)) OPS_FAIL(MI355Q_ERR_SHAPE, "op_cpy: element counts differ");
     if (dst->type == MI355Q_TYPE_Q8_0 || dst->type == MI355Q_TYPE_Q4_0) {
         if (cpy_to_q8_0(a, dst, nullptr, 0, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 -> q8_0 / q4_0 needs a contiguous destination and source rows of whole 32-blocks");
         OPS_LAUNCHED();
     }
-    if (a->type < 0 || a->type > 1 || dst->type < 0 || dst->type > 1) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 / f16 only");
+    if (!cpy_type(a->type) || !cpy_type(dst->type)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 / f16 / bf16 only");
     const int64_t n = nelements(dst);
     if (n == 0) return MI355Q_OK;
     if (!cpy_fast(a, dst, nullptr, 0, (hipStream_t) stream))
@@ -1098,7 +1215,7 @@ int mi355q_op_cpy_indirect(const mi355q_tensor * a, const mi355q_tensor * dst, v
         if (cpy_to_q8_0(a, dst, (char * const *) dest_table, index, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 -> q8_0 / q4_0 needs a contiguous destination and source rows of whole 32-blocks");
         OPS_LAUNCHED();
     }
-    if (a->type < 0 || a->type > 1 || dst->type < 0 || dst->type > 1) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 / f16 only");
+    if (!cpy_type(a->type) || !cpy_type(dst->type)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 / f16 / bf16 only");
     const int64_t n = nelements(dst);
     if (n == 0) return MI355Q_OK;
     if (!cpy_fast(a, dst, (char * const *) dest_table, index, (hipStream_t) stream))
@@ -1157,7 +1274,7 @@ int mi355q_op_soft_max(const mi355q_tensor * a, const mi355q_tensor * mask, cons
 
 int mi355q_op_get_rows(const mi355q_tensor * a, const mi355q_tensor * ids, const mi355q_tensor * dst, void * stream) {
     if (!a || !ids || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_get_rows: null tensor");
-    if ((a->type != 0 && a->type != 1) || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_get_rows: f32 / f16 rows to f32");
+    if ((a->type != 0 && a->type != 1 && a->type != MI355Q_T_BF16) || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_get_rows: f32 / f16 / bf16 rows to f32");
     if (dst->ne[0] != a->ne[0] || dst->ne[1] != ids->ne[0] || dst->ne[2] != ids->ne[1] || dst->ne[3] != ids->ne[2] || a->ne[2] != ids->ne[1])
         OPS_FAIL(MI355Q_ERR_SHAPE, "op_get_rows: shapes (dst [ne00, ne10, ne11, ne12], ne02 == ne11)");
     const int64_t n = nelements(dst);
@@ -1229,17 +1346,18 @@ int mi355q_op_rope(const mi355q_tensor * a, const int32_t * pos, const float * f
 
 int mi355q_op_mul_mat_f(const mi355q_tensor * a, const mi355q_tensor * b, const mi355q_tensor * dst, void * stream) {
     if (!a || !b || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_mul_mat_f: null tensor");
-    if ((a->type != 0 && a->type != 1) || b->type != 0 || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: src0 f16/f32, src1 and dst f32");
+    if ((a->type != 0 && a->type != 1 && a->type != MI355Q_T_BF16) || b->type != 0 || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: src0 f16/bf16/f32, src1 and dst f32");
     if (a->ne[0] != b->ne[0] || dst->ne[0] != a->ne[1] || dst->ne[1] != b->ne[1] || dst->ne[2] != b->ne[2] || dst->ne[3] != b->ne[3] ||
         a->ne[2] <= 0 || a->ne[3] <= 0 || b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3]) OPS_FAIL(MI355Q_ERR_SHAPE, "op_mul_mat_f: shapes");
     if (a->nb[0] != (a->type == 0 ? 4 : 2) || b->nb[0] != 4) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: the k dimension must be contiguous in both operands");
     const int64_t n_out = nelements(dst);
     if (n_out == 0) return MI355Q_OK;
-    // many src1 rows and an f16 src0 (prefill attention): matrix cores
-    if (a->type == 1 && b->ne[1] >= 16 && dst->ne[0] >= 16 && a->ne[0] % 16 == 0 && dst->ne[2] * dst->ne[3] <= 65535 &&
+    // many src1 rows and an f16 / bf16 src0 (prefill attention): matrix cores
+    if (a->type != 0 && b->ne[1] >= 16 && dst->ne[0] >= 16 && a->ne[0] % 16 == 0 && dst->ne[2] * dst->ne[3] <= 65535 &&
         !(((uintptr_t) a->data | (uintptr_t) a->nb[1] | (uintptr_t) a->nb[2] | (uintptr_t) a->nb[3] | (uintptr_t) b->data | (uintptr_t) b->nb[1] | (uintptr_t) b->nb[2] | (uintptr_t) b->nb[3]) & 15)) {
-        hipLaunchKernelGGL(k_mul_mat_f16_mfma<false>, dim3((unsigned) ((dst->ne[0] + MMF_T - 1) / MMF_T), (unsigned) ((dst->ne[1] + MMF_T - 1) / MMF_T), (unsigned) (dst->ne[2] * dst->ne[3])),
-                           dim3(256), 0, (hipStream_t) stream, to_d(a), to_d(b), to_d(dst));
+        const dim3 g((unsigned) ((dst->ne[0] + MMF_T - 1) / MMF_T), (unsigned) ((dst->ne[1] + MMF_T - 1) / MMF_T), (unsigned) (dst->ne[2] * dst->ne[3]));
+        if (a->type == MI355Q_T_BF16) hipLaunchKernelGGL((k_mul_mat_f16_mfma<false, true>), g, dim3(256), 0, (hipStream_t) stream, to_d(a), to_d(b), to_d(dst));
+        else                          hipLaunchKernelGGL((k_mul_mat_f16_mfma<false>),       g, dim3(256), 0, (hipStream_t) stream, to_d(a), to_d(b), to_d(dst));
         OPS_LAUNCHED();
     }
     const int64_t groups_per_col = (dst->ne[0] + MMF_ROWS - 1) / MMF_ROWS, n_groups = groups_per_col * dst->ne[1] * dst->ne[2] * dst->ne[3];
@@ -1259,8 +1377,9 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
                              void * workspace, size_t workspace_bytes, void * stream) {
     if (!q || !k || !v || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: null tensor");
     const bool kv_q80 = (k->type == MI355Q_TYPE_Q8_0 && v->type == MI355Q_TYPE_Q8_0) || (k->type == MI355Q_TYPE_Q4_0 && v->type == MI355Q_TYPE_Q4_0);     // a quantized cache
+    const bool kv_bf16 = k->type == MI355Q_T_BF16 && v->type == MI355Q_T_BF16;
     const int  kv_bb = k->type == MI355Q_TYPE_Q4_0 ? 18 : 34;
-    if (q->type != 0 || !((k->type == 1 && v->type == 1) || kv_q80) || dst->type != 0 || (mask && mask->type != 1)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, k / v both f16, both q8_0 or both q4_0, mask f16, dst f32");
+    if (q->type != 0 || !((k->type == 1 && v->type == 1) || kv_q80 || kv_bf16) || dst->type != 0 || (mask && mask->type != 1)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, k / v both f16, both bf16, both q8_0 or both q4_0, mask f16, dst f32");
     const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
     if (q->ne[0] != DK || v->ne[1] != n_kv || k->ne[2] <= 0 || v->ne[2] <= 0 || n_head % k->ne[2] || n_head % v->ne[2] || k->ne[3] <= 0 || v->ne[3] <= 0 ||
         nb3 % k->ne[3] || nb3 % v->ne[3] || dst->ne[0] != DV || dst->ne[1] != n_head || dst->ne[2] != N || dst->ne[3] != nb3)
@@ -1298,19 +1417,30 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
             return mi355q_op_flash_attn_ext(q, &k16, &v16, mask, dst, logit_softcap != 0.0f ? scale * logit_softcap : scale, max_bias, logit_softcap, workspace, sc_bytes, stream);
         }
     }
-    if (kv_q80) {                                            // a quantized cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
-        if (DK % 32 || DV % 32 || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q8_0 cache needs head sizes of whole 32-blocks and n_kv <= 8192");
-        const size_t lds = (size_t) (2 * n_kv + DK / 32 + DK / 4) * 4;
+    // Many query rows (prefill) and scratch for the scores: the three steps of the definition on the matrix-core kernels -- scores = K q
+    // (k_mul_mat_f16_mfma), row softmax with the f16 mask (k_soft_max), out = P V with V read transposed (k_mul_mat_f16_mfma<true>).  One
+    // workgroup per row (below) re-streams K and V for every row: 5x slower for a 512-token batch.  A bf16 cache takes the bf16 form of the
+    // kernels directly (its exponent range does not fit f16 scratch); P is rounded to bf16 there, the one deviation from the CPU.
+    auto al16 = [](const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 15) == 0; };
+    const bool mfma = N >= 16 && logit_softcap == 0.0f && workspace && workspace_bytes >= (size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4 &&
+                      DK % 16 == 0 && DV % 16 == 0 && n_kv % 16 == 0 && al16(q) && al16(k) && al16(v) && n_head * nb3 <= 65535 && (!mask || mask->nb[1] == 2 * n_kv);
+    if (kv_q80 || (kv_bf16 && !mfma)) {                      // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
+        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a q8_0 / q4_0 cache needs head sizes of whole 32-blocks; q8_0 / q4_0 / bf16 need n_kv <= 8192");
+        const size_t lds = (size_t) (2 * n_kv + (kv_bf16 ? DK : DK / 32 + DK / 4)) * 4;
         static bool attr_q80[64] = {};
         if (lds > 48 * 1024) {
             int dev = 0; (void) hipGetDevice(&dev); dev = dev >= 0 && dev < 64 ? dev : 0;
             if (!attr_q80[dev]) {
                 if (hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q8_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q4_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) OPS_FAIL(MI355Q_ERR_HIP, "op_flash_attn_ext: LDS attribute");
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q4_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_T_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) OPS_FAIL(MI355Q_ERR_HIP, "op_flash_attn_ext: LDS attribute");
                 attr_q80[dev] = true;
             }
         }
-        if (k->type == MI355Q_TYPE_Q8_0)
+        if (kv_bf16)
+            hipLaunchKernelGGL(k_flash_attn_ext_q80<MI355Q_T_BF16>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream,
+                               to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
+        else if (k->type == MI355Q_TYPE_Q8_0)
             hipLaunchKernelGGL(k_flash_attn_ext_q80<MI355Q_TYPE_Q8_0>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream,
                                to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
         else
@@ -1318,19 +1448,14 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
                                to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
         OPS_LAUNCHED();
     }
-    // Many query rows (prefill) and scratch for the scores: the three steps of the definition on the matrix-core kernels -- scores = K q
-    // (k_mul_mat_f16_mfma), row softmax with the f16 mask (k_soft_max), out = P V with V read transposed (k_mul_mat_f16_mfma<true>).  One
-    // workgroup per row (below) re-streams K and V for every row: 5x slower for a 512-token batch.
     {
-        const size_t need = (size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4;
-        auto al16 = [](const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 15) == 0; };
-        if (N >= 16 && logit_softcap == 0.0f && workspace && workspace_bytes >= need && DK % 16 == 0 && DV % 16 == 0 && n_kv % 16 == 0 &&
-            al16(q) && al16(k) && al16(v) && n_head * nb3 <= 65535 && (!mask || mask->nb[1] == 2 * n_kv)) {
+        if (mfma) {
             mi355q_tensor sc; sc.data = workspace; sc.type = 0;
             sc.ne[0] = n_kv; sc.ne[1] = N; sc.ne[2] = n_head; sc.ne[3] = nb3;
             sc.nb[0] = 4; sc.nb[1] = 4 * n_kv; sc.nb[2] = sc.nb[1] * N; sc.nb[3] = sc.nb[2] * n_head;
             const dim3 g1((unsigned) ((n_kv + MMF_T - 1) / MMF_T), (unsigned) ((N + MMF_T - 1) / MMF_T), (unsigned) (n_head * nb3));
-            hipLaunchKernelGGL(k_mul_mat_f16_mfma<false>, g1, dim3(256), 0, (hipStream_t) stream, to_d(k), to_d(q), to_d(&sc));
+            if (kv_bf16) hipLaunchKernelGGL((k_mul_mat_f16_mfma<false, true>), g1, dim3(256), 0, (hipStream_t) stream, to_d(k), to_d(q), to_d(&sc));
+            else         hipLaunchKernelGGL((k_mul_mat_f16_mfma<false>),       g1, dim3(256), 0, (hipStream_t) stream, to_d(k), to_d(q), to_d(&sc));
             const int rc = mi355q_op_soft_max(&sc, mask, &sc, scale, max_bias, stream);     // in place, row by row
             if (rc != MI355Q_OK) return rc;
             mi355q_tensor vt = *v;                             // [K = n_kv, M = DV] with M contiguous: the transposed-source form
@@ -1339,7 +1464,8 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
             od.ne[0] = DV; od.ne[1] = N; od.ne[2] = n_head; od.ne[3] = nb3;
             od.nb[1] = dst->nb[2]; od.nb[2] = dst->nb[1];
             const dim3 g2((unsigned) ((DV + MMF_T - 1) / MMF_T), (unsigned) ((N + MMF_T - 1) / MMF_T), (unsigned) (n_head * nb3));
-            hipLaunchKernelGGL(k_mul_mat_f16_mfma<true>, g2, dim3(256), 0, (hipStream_t) stream, to_d(&vt), to_d(&sc), to_d(&od));
+            if (kv_bf16) hipLaunchKernelGGL((k_mul_mat_f16_mfma<true, true>), g2, dim3(256), 0, (hipStream_t) stream, to_d(&vt), to_d(&sc), to_d(&od));
+            else         hipLaunchKernelGGL((k_mul_mat_f16_mfma<true>),       g2, dim3(256), 0, (hipStream_t) stream, to_d(&vt), to_d(&sc), to_d(&od));
             OPS_LAUNCHED();
         }
     }

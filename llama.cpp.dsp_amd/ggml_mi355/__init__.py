@@ -158,6 +158,7 @@ def lib() -> C.CDLL:
     L.mi355q_op_scale.argtypes = [TP, TP, C.c_float, vp]
     L.mi355q_op_argsort.argtypes = [TP, TP, i32, vp]
     L.mi355q_op_sum_rows.argtypes = [TP, TP, vp]
+    L.mi355q_op_cpy_indirect.argtypes = [TP, TP, vp, i32, vp]
     L.mi355q_mul_mat_id_workspace.restype = sz; L.mi355q_mul_mat_id_workspace.argtypes = [i32, i64, i64, i64, i64, i64, i64]
     L.mi355q_mul_mat_id.argtypes = [i32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, vp, i64, i64, i64, i64, vp, sz, i32, vp]
     _lib = L
@@ -399,16 +400,16 @@ class Plan:
 
 
 def _td(t) -> _Tensor:
-    """torch tensor (f32/f16, <= 4 dims, torch dims are ggml dims reversed) -> mi355q_tensor with ggml-ordered ne/nb."""
+    """torch tensor (f32/f16/bf16, <= 4 dims, torch dims are ggml dims reversed) -> mi355q_tensor with ggml-ordered ne/nb."""
     torch = _torch()
-    assert t.dtype in (torch.float32, torch.float16) and 1 <= t.dim() <= 4
+    assert t.dtype in (torch.float32, torch.float16, torch.bfloat16) and 1 <= t.dim() <= 4
     shape = list(t.shape)[::-1] + [1] * (4 - t.dim())
     es = t.element_size()
     strides = [s * es for s in list(t.stride())[::-1]]
     nb = strides + [0] * (4 - t.dim())
     for i in range(t.dim(), 4):                       # ggml convention for the padded dims: nb[i] = nb[i-1] * ne[i-1]
         nb[i] = nb[i - 1] * shape[i - 1]
-    d = _Tensor(); d.data = t.data_ptr(); d.type = 0 if t.dtype == torch.float32 else 1
+    d = _Tensor(); d.data = t.data_ptr(); d.type = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 30}[t.dtype]
     for i in range(4):
         d.ne[i] = shape[i]; d.nb[i] = nb[i]
     return d
@@ -475,7 +476,7 @@ def op_unary_mul(uop: int, a, b):
 
 def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0"):
     """GGML_OP_FLASH_ATTN_EXT: q f32 [B, H, N, DK] (torch order), k f16 [Bk, Hk, n_kv, DK], v f16 [Bv, Hv, n_kv, DV], mask f16 [>= N, >= n_kv]
-    or None -> f32 [B, N, H, DV]."""
+    or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 cache)."""
     torch = _torch()
     out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3]), dtype=torch.float32, device=q.device)
     ws, wsb = (_workspace(torch, int(lib().mi355q_op_flash_attn_ext_workspace(v.shape[3], q.shape[2], q.shape[1], q.shape[0], k.shape[2])), q.device)
@@ -490,9 +491,19 @@ def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_
 
 
 def op_cpy(a, out, kv: str = "q8_0"):
-    """GGML_OP_CPY; a uint8 `out` of shape [..., n / 32 * 34] (kv "q8_0") or [..., n / 32 * 18] ("q4_0") is a quantized destination (KV cache rows)."""
+    """GGML_OP_CPY among f32 / f16 / bf16 tensors; a uint8 `out` of shape [..., n / 32 * 34] (kv "q8_0") or [..., n / 32 * 18] ("q4_0") is a quantized destination (KV cache rows)."""
     td_out = _td_q8_0(out, kv) if out.dtype == _torch().uint8 else _td(out)
     _check(lib().mi355q_op_cpy(C.byref(_td(a)), C.byref(td_out), _stream(_torch())), "op_cpy")
+    return out
+
+
+def op_cpy_indirect(a, out, table, index: int):
+    """GGML_OP_CPY into a destination resolved on the device: `out` gives the type, shape and strides, and the data pointer is read from
+    table[index] (`table`: a device int64 tensor of addresses) when the kernel runs -- the KV store of a replayed launch graph."""
+    torch = _torch()
+    assert table.dtype == torch.int64 and table.is_cuda and 0 <= index < table.numel()
+    td_out = _td_q8_0(out) if out.dtype == torch.uint8 else _td(out)
+    _check(lib().mi355q_op_cpy_indirect(C.byref(_td(a)), C.byref(td_out), table.data_ptr(), index, _stream(torch)), "op_cpy_indirect")
     return out
 
 
@@ -516,7 +527,7 @@ def op_rope(a, pos, n_dims: int, mode: int = 0, freq_factors=None, n_ctx_orig: i
 
 
 def op_get_rows(a, ids, out=None):
-    """GGML_OP_GET_ROWS: a [.., n_rows, ne0] (f32/f16), ids int32 [.., n_ids] -> f32 [.., n_ids, ne0]."""
+    """GGML_OP_GET_ROWS: a [.., n_rows, ne0] (f32/f16/bf16), ids int32 [.., n_ids] -> f32 [.., n_ids, ne0]."""
     torch = _torch()
     assert ids.dtype == torch.int32
     if out is None:
@@ -554,7 +565,7 @@ def op_scale(a, scale: float, out=None):
 
 
 def op_mul_mat_f(a, b, out=None):
-    """GGML_OP_MUL_MAT with an f16/f32 src0: a [.., M, K], b [.., N, K] (torch order) -> [.., N, M] f32."""
+    """GGML_OP_MUL_MAT with an f16/bf16/f32 src0: a [.., M, K], b [.., N, K] (torch order) -> [.., N, M] f32."""
     torch = _torch()
     if out is None:
         out = torch.empty(tuple(b.shape[:-2]) + (b.shape[-2], a.shape[-2]), dtype=torch.float32, device=b.device)
