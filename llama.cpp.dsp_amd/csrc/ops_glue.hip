@@ -649,7 +649,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
                 if (softcap != 0.0f) s = softcap * tanhf(s);
                 if (mp) {
                     const float mv = __fmul_rn(slope, __half2float(mp[j]));
-                    s = (seq && mv == -INFINITY) ? -INFINITY : __fadd_rn(s, mv);     // (seq: a masked position is SKIPPED by the CPU whatever its cache row holds)
+                    s = mv == -INFINITY ? -INFINITY : __fadd_rn(s, mv);     // (a masked position is SKIPPED by the CPU whatever its cache row holds)
                 }
                 fa_s[j] = s;
             }
@@ -719,7 +719,13 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
     if (g < groups) {
         const char * vb = v.data + j_lo * v.nb[1] + hv * v.nb[2] + bv * v.nb[3] + 2 * (int64_t) e;
 #pragma unroll 8
-        for (int64_t j = g; j < n_kv; j += groups) acc += fa_s[j] * __half2float(*(const __half *) (vb + j * v.nb[1]));
+        for (int64_t j = g; j < n_kv; j += groups) {
+            // a zero probability (a masked position) adds nothing, whatever the cache row holds: 0 * NaN / Inf must not reach the sum, as the CPU
+            // never reads such a row (finite rows: no bit changes, 0 * v = +-0 leaves acc as it is)
+            const float p = fa_s[j], vv = __half2float(*(const __half *) (vb + j * v.nb[1]));
+            const float t = acc + p * vv;
+            acc = p != 0.0f ? t : acc;
+        }
     }
     __syncthreads();                                                        // everyone is done reading the probabilities
     float * part = fa_s;                                                     // (at least FA_THREADS floats of LDS are guaranteed by the launcher)

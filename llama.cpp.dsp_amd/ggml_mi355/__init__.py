@@ -454,10 +454,11 @@ def op_rms_norm(a, eps: float, out=None):
     return out
 
 
-def op_add_rms_norm_mul(a, eps: float, b=None, weight=None, want_sum: bool = False):
-    """Fused [a + b ->] rms_norm [-> * weight]; returns out or (out, sum).  Bit-identical to the separate ops (include/mi355q.h)."""
+def op_add_rms_norm_mul(a, eps: float, b=None, weight=None, want_sum: bool = False, out=None):
+    """Fused [a + b ->] rms_norm [-> * weight]; returns out or (out, sum).  Bit-identical to the separate ops (include/mi355q.h).
+    `out` may be `a` or `b` itself (row r of dst is row r of the operand, owned by one workgroup)."""
     torch = _torch()
-    out = torch.empty_like(a, memory_format=torch.contiguous_format)
+    out = out if out is not None else torch.empty_like(a, memory_format=torch.contiguous_format)
     s = torch.empty_like(a, memory_format=torch.contiguous_format) if (want_sum and b is not None) else None
     if weight is not None and (weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != a.shape[-1]):
         raise ValueError("weight must be a contiguous f32 vector of the row length")

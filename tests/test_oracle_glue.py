@@ -146,3 +146,35 @@ def test_flash_attn_ext_q8_0_cache_bitexact(cfg, kv):
     assert pr.returncode == 0, pr.stderr[-1500:]
     st = json.loads(pr.stdout.strip().splitlines()[-1])
     assert st["differ"] == 0.0, st
+
+
+# ---- the shapes that select the device's other soft-max and rms-norm kernels (tests/test_gpu_glue_branches.py) -------------------------------
+def _f16_mask(rng, rows, ne0):
+    """mask values f16 represents exactly (-inf among them): the f32 mask the shim takes stands for the f16 mask the graph uses"""
+    m = rng.standard_normal((rows, ne0)).astype(np.float32)
+    m[rng.random((rows, ne0)) < 0.2] = -np.inf
+    m[:, 0] = 0.0
+    return m.astype(np.float16).astype(np.float32)
+
+
+@pytest.mark.parametrize("heads,ne0,max_bias", [(3, 2049, 0.0), (3, 2049, 8.0), (2, 32768, 0.0), (2, 32768, 8.0), (12, 300, 8.0), (12, 4113, 8.0),
+                                                 (40, 1500, 8.0), (40, 2049, 8.0)], ids=str)
+def test_soft_max_long_rows_and_alibi_heads(ref, heads, ne0, max_bias):
+    """glue.soft_max against the reference at rows of 2049 and 32768 columns and with ALiBi over 12 and 40 heads (m1 slopes), per element relative:
+    numpy's expf and the C library's differ in the last place now and then."""
+    rng = np.random.default_rng(heads * 100000 + ne0)
+    kq = (rng.standard_normal((1, heads, 3, ne0)) * 3).astype(np.float32)
+    mask = _f16_mask(rng, 3, ne0)
+    r = ref.glue_op(12, kq, mask, fparams=[0.125, max_bias])
+    o = glue.soft_max(kq, mask, 0.125, max_bias)
+    assert np.array_equal(o == 0, r == 0)
+    nz = r != 0
+    e = float((np.abs(o[nz].astype(np.float64) - r[nz]) / r[nz]).max())
+    assert e <= 1.5e-6, e                                                   # (measured 3.8e-7 at most: three ulp)
+
+
+@pytest.mark.parametrize("ne0", [30, 4097, 20480])
+def test_rms_norm_bitexact_other_kernels(ref, ne0):
+    rng = np.random.default_rng(ne0)
+    x = (rng.standard_normal((1, 2, 3, ne0)) * rng.uniform(0.01, 30.0, (1, 2, 3, 1))).astype(np.float32)
+    assert np.array_equal(bits(glue.rms_norm(x, 1e-5)), bits(ref.glue_op(10, x, fparams=[1e-5]))), ne0
