@@ -213,6 +213,15 @@ int    mi355q_mul_mat_id(int type, const void *w, int64_t w_stride_bytes, int64_
  * run(): asynchronous on `stream`.  status(): synchronizes; 1 = a poll timed out (plan unusable).                         */
 #define MI355Q_STAGE_DEPENDS  0x1    /* (API version 1; accepted and ignored: dependencies follow from the operand addresses) */
 #define MI355Q_STAGE_NO_PLAIN 0x2    /* do not store plain f32 copies of this stage's outputs                               */
+/* ATTN stages over a QUANTIZED KV cache (-ctk q8_0 -ctv q8_0 / q4_0): both the K and the V cache hold blocks of that type (no bit: f16).
+ * Block b (32 elements) of kv head g's row at position j is at  cache + j*nb_pos + g*nb_head + b*BB,  BB = 34 (q8_0) or 18 (q4_0); addresses
+ * and strides must be even.  Only the flash layout (V rows per position, v_nb_dim = BB) is taken, with head_dim % 32 == 0.  This token's K and
+ * V rows are quantized as mi355q_op_cpy (f32 -> q8_0 / q4_0) quantizes them and stored as contiguous rows at *k_dst / *v_dst (v_dst_nb is
+ * ignored); the scores and P.V read them back as blocks, as the CPU does.  One split per head: the output is mi355q_op_flash_attn_ext's on the
+ * same cache, bit for bit; several (windows above 256 positions) merge per-split F32 accumulators.  plan_create refuses a
+ * window whose per-split K / V blocks do not fit the LDS (the message gives the limit) and the ring engine (MI355Q_PLAN_ENGINE=ring).      */
+#define MI355Q_STAGE_KV_Q8_0  0x4
+#define MI355Q_STAGE_KV_Q4_0  0x8
 #define MI355Q_STAGE_GEMV 0
 #define MI355Q_STAGE_ATTN 1
 #define MI355Q_X_PLAIN     0

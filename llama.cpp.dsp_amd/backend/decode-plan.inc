@@ -124,7 +124,11 @@ struct mi355_plan_matcher {
             memcpy(&scale, (const float *) sm->op_params + 0, 4); memcpy(&max_bias, (const float *) sm->op_params + 1, 4);
         }
         if (max_bias != 0.0f || softcap != 0.0f) return false;
-        if (kview->type != GGML_TYPE_F16 || vview->type != GGML_TYPE_F16 || !kview->view_src || !vview->view_src || kview->nb[0] != 2) return false;
+        // the cache: f16, or (flash graphs only) both K and V in Q8_0 or both in Q4_0 blocks (-ctk q8_0 -ctv q8_0): the stage flag MI355Q_STAGE_KV_*
+        const enum ggml_type kvt = kview->type;
+        const bool kv_quant = fa && (kvt == GGML_TYPE_Q8_0 || kvt == GGML_TYPE_Q4_0);
+        const size_t kv_nb0 = kv_quant ? ggml_type_size(kvt) : 2;                              // bytes per element (f16) or per 32-block
+        if ((kvt != GGML_TYPE_F16 && !kv_quant) || vview->type != kvt || !kview->view_src || !vview->view_src || kview->nb[0] != kv_nb0) return false;
         const struct ggml_tensor * rq = mi355_skip_views(qperm);
         if (!rq || rq->op != GGML_OP_ROPE) return false;
         const struct ggml_tensor * qm = mat_behind(rq->src[0]);
@@ -141,7 +145,8 @@ struct mi355_plan_matcher {
             if (n->src[1]->view_src == kview->view_src) { if (ck) return false; ck = n; }
             else if (n->src[1]->view_src == vview->view_src) { if (cv) return false; cv = n; }
         }
-        if (!ck || !cv || ck->src[1]->type != GGML_TYPE_F16 || cv->src[1]->type != GGML_TYPE_F16) return false;
+        if (!ck || !cv || ck->src[1]->type != kvt || cv->src[1]->type != kvt) return false;
+        if (kv_quant && (ck->src[0]->type != GGML_TYPE_F32 || cv->src[0]->type != GGML_TYPE_F32)) return false;       // CPY f32 -> q8_0 / q4_0
         const struct ggml_tensor * rk = mi355_skip_views(ck->src[0]);
         if (!rk || rk->op != GGML_OP_ROPE || rk->src[1] != rq->src[1] || rk->src[2] != rq->src[2]) return false;
         if (memcmp(rk->op_params, rq->op_params, sizeof(rk->op_params)) != 0) return false;
@@ -174,14 +179,15 @@ struct mi355_plan_matcher {
         a->freq_factors = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
         a->k_cache = kview->data; a->k_nb_pos = (int64_t) kview->nb[1]; a->k_nb_head = (int64_t) kview->nb[2];
         a->v_cache = vview->data;
-        if (fa) { if (vview->nb[0] != 2 || vview->ne[0] != hd || vview->ne[1] != n_kv) return false; a->v_nb_dim = 2; a->v_nb_pos = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
+        if (fa) { if (vview->nb[0] != kv_nb0 || vview->ne[0] != hd || vview->ne[1] != n_kv) return false; a->v_nb_dim = (int64_t) kv_nb0; a->v_nb_pos = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
         else    { if (vview->nb[0] != 2 || vview->ne[0] != n_kv || vview->ne[1] != hd) return false; a->v_nb_pos = 2; a->v_nb_dim = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
         a->k_dst = (void * const *) (dest_table + cpy_ordinal[(size_t) idx(ck)]);
         a->v_dst = (void * const *) (dest_table + cpy_ordinal[(size_t) idx(cv)]);
-        if (ck->src[1]->nb[0] != 2 || !ggml_is_contiguous(ck->src[1])) return false;            // the K row is stored contiguously
+        if (ck->src[1]->nb[0] != kv_nb0 || !ggml_is_contiguous(ck->src[1])) return false;       // the K row is stored contiguously
         const struct ggml_tensor * vd = cv->src[1];
         a->v_dst_nb = vd->ne[0] == 1 ? (int64_t) vd->nb[1] : (int64_t) vd->nb[0];
         if (vd->ne[0] != 1 && !ggml_is_contiguous(vd)) return false;
+        if (kv_quant && (vd->ne[0] == 1 || vd->nb[0] != kv_nb0)) return false;                   // (a quantized V row is stored contiguously too)
         a->mask = mask ? mask->data : nullptr; a->mask_f16 = mask && mask->type == GGML_TYPE_F16;
         if (mask_cast) mask_casts.insert(mask_cast);
         a->n_head = (int) n_head; a->n_head_kv = (int) n_head_kv; a->head_dim = (int) hd; a->n_kv = (int) n_kv;
@@ -190,13 +196,14 @@ struct mi355_plan_matcher {
         if (kview->view_src->buffer == nullptr || !mi355_buft_is_ours(kview->view_src->buffer->buft) || !mi355_buft_is_ours(vview->view_src->buffer->buft)) return false;
 
         if (getenv("MI355_PLAN_DEBUG"))
-            fprintf(stderr, "MI355 plan attn: q %p k %p v %p pos %p | n_head %d n_head_kv %d hd %d n_kv %d | rope n_dims %d mode %d base %g | k_cache %p nb_pos %lld nb_head %lld | v_cache %p nb_pos %lld nb_dim %lld nb_head %lld | "
+            fprintf(stderr, "MI355 plan attn: q %p k %p v %p pos %p | n_head %d n_head_kv %d hd %d n_kv %d | rope n_dims %d mode %d base %g | kv %s | k_cache %p nb_pos %lld nb_head %lld | v_cache %p nb_pos %lld nb_dim %lld nb_head %lld | "
                             "cpy slots k %d v %d (k dst now %p, v dst now %p) v_dst_nb %lld | mask %p f16 %d scale %g | out %p\n",
-                    (void *) a->q, (void *) a->k, (void *) a->v, (void *) a->pos, a->n_head, a->n_head_kv, a->head_dim, a->n_kv, a->rope.n_dims, a->rope.mode, a->rope.freq_base,
+                    (void *) a->q, (void *) a->k, (void *) a->v, (void *) a->pos, a->n_head, a->n_head_kv, a->head_dim, a->n_kv, a->rope.n_dims, a->rope.mode, a->rope.freq_base, ggml_type_name(kvt),
                     a->k_cache, (long long) a->k_nb_pos, (long long) a->k_nb_head, a->v_cache, (long long) a->v_nb_pos, (long long) a->v_nb_dim, (long long) a->v_nb_head,
                     cpy_ordinal[(size_t) idx(ck)], cpy_ordinal[(size_t) idx(cv)], ck->data, cv->data, (long long) a->v_dst_nb, a->mask, a->mask_f16, a->scale, (void *) a->out);
         mi355q_stage st; memset(&st, 0, sizeof(st));
         st.kind = MI355Q_STAGE_ATTN; st.attn = a; st.flags = MI355Q_STAGE_NO_PLAIN;
+        if (kv_quant) st.flags |= kvt == GGML_TYPE_Q8_0 ? MI355Q_STAGE_KV_Q8_0 : MI355Q_STAGE_KV_Q4_0;
         b.stages.push_back(st);
         b.anchor.push_back(idx(fa ? fa : kq));
         b.outs.push_back({ top });

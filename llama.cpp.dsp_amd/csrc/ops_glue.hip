@@ -19,6 +19,7 @@
 
 #include "mi355q_common.h"
 #include "act_quant.cuh"
+#include "fa_quant.cuh"
 
 namespace mi355q {
 
@@ -296,14 +297,9 @@ __global__ void __launch_bounds__(256) k_cpy_f32_q8_0(const TensorD a, char * ds
         const int64_t a0 = e % a.ne[0], ar = e / a.ne[0], a1 = ar % a.ne[1], ar2 = ar / a.ne[1], a2 = ar2 % a.ne[2], a3 = ar2 / a.ne[2];
         const float * src = (const float *) (a.data + a0 * 4 + a1 * a.nb[1] + a2 * a.nb[2] + a3 * a.nb[3]);
         const float4 v = make_float4(src[0], src[1], src[2], src[3]);
-        uint32_t q; float d; int sum;
-        q80_group8<false>(v, q, d, sum);
-        if (b0 < n_blocks) {
-            char * blk = dst + 34 * b;                           // 2-byte aligned: the quants are stored as halves of a word
-            if (lane8 == 0) *(__half *) blk = __float2half_rn(d);
-            *(uint16_t *) (blk + 2 + 4 * lane8) = (uint16_t) (q & 0xFFFFu);
-            *(uint16_t *) (blk + 4 + 4 * lane8) = (uint16_t) (q >> 16);
-        }
+        uint32_t q; float d;
+        kv_quant_group8<MI355Q_TYPE_Q8_0>(v, q, d);
+        if (b0 < n_blocks) kv_store_group8<MI355Q_TYPE_Q8_0>(dst + 34 * b, lane8, q, d);     // 2-byte aligned: the quants are stored as halves of a word
     }
 }
 
@@ -317,26 +313,9 @@ __global__ void __launch_bounds__(256) k_cpy_f32_q4_0(const TensorD a, char * ds
         const int64_t e = 32 * b + 4 * lane8;
         const int64_t a0 = e % a.ne[0], ar = e / a.ne[0], a1 = ar % a.ne[1], ar2 = ar / a.ne[1], a2 = ar2 % a.ne[2], a3 = ar2 / a.ne[2];
         const float * src = (const float *) (a.data + a0 * 4 + a1 * a.nb[1] + a2 * a.nb[2] + a3 * a.nb[3]);
-        const float x[4] = { src[0], src[1], src[2], src[3] };
-        float amax = 0.0f, mx = 0.0f;                            // this lane's first element of largest magnitude
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (amax < fabsf(x[i])) { amax = fabsf(x[i]); mx = x[i]; }
-        const float gmax = oct_max(amax);                         // the block's largest magnitude; its first holder is the lowest lane that has it
-        const unsigned long long holders = __ballot(amax == gmax);
-        const int first = __ffs((int) ((holders >> (lane & ~7)) & 0xFFull)) - 1;
-        const float bmax = __shfl(mx, (lane & ~7) + first, 64);
-        const float d = __fdiv_rn(bmax, -8.0f), id = d != 0.0f ? __fdiv_rn(1.0f, d) : 0.0f;
-        uint32_t nib = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const int qi = min(15, (int) (int8_t) __fadd_rn(__fmul_rn(x[i], id), 8.5f)); nib |= (uint32_t) (qi & 0xFF) << (8 * i); }
-        const uint32_t hi = (uint32_t) dpp_i<0x104>((int) nib);  // row_shl:4 -- lanes 0..3 of the group get elements 16..31 from lanes 4..7
-        if (b0 < n_blocks && lane8 < 4) {
-            char * blk = dst + 18 * b;
-            const uint32_t w = (nib & 0x0F0F0F0Fu) | ((hi & 0x0F0F0F0Fu) << 4);
-            if (lane8 == 0) *(__half *) blk = __float2half_rn(d);
-            *(uint16_t *) (blk + 2 + 4 * lane8) = (uint16_t) (w & 0xFFFFu);
-            *(uint16_t *) (blk + 4 + 4 * lane8) = (uint16_t) (w >> 16);
-        }
+        uint32_t w; float d;
+        kv_quant_group8<MI355Q_TYPE_Q4_0>(make_float4(src[0], src[1], src[2], src[3]), w, d);
+        if (b0 < n_blocks) kv_store_group8<MI355Q_TYPE_Q4_0>(dst + 18 * b, lane8, w, d);
     }
 }
 
@@ -767,12 +746,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     if constexpr (KVT == MI355Q_T_BF16) {
         if (tid < DK) qd[tid] = bf16_round(((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]))[tid]);
     } else if (tid < ((DK / 4 + 63) & ~63)) {
-        const float * qp = (const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]);
-        const int e = 4 * tid;
-        const float4 x = e < DK ? make_float4(qp[e], qp[e + 1], qp[e + 2], qp[e + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        uint32_t pq; float dq; int sum;
-        q80_group8<true>(x, pq, dq, sum);                                     // (round half to even: the CPU's SIMD quantize_row_q8_0, ggml-cpu-quants.c:842-845)
-        if (e < DK) { qq[tid] = pq; if ((tid & 7) == 0) qd[tid >> 3] = __half2float(__float2half_rn(dq)); }
+        fa_quantize_q((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]), tid, DK, qq, qd);     // (fa_quant.cuh)
     }
     __syncthreads();
     // ---- scores: one position per thread
@@ -804,30 +778,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
             if (softcap != 0.0f) s = softcap * tanhf(s);
             s = __fadd_rn(s, mv);
         } else if (mv != -INFINITY) {                                         // (a masked position is skipped by the CPU whatever its cache row holds)
-            const char * row = k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3];
-            float acc[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-            for (int blk = 0; blk < nblk; ++blk) {
-                const char * kb = row + BB * blk;
-                const float dd = __fmul_rn(__half2float(*(const __half *) kb), qd[blk]);
-                if constexpr (KVT == MI355Q_TYPE_Q8_0) {
-#pragma unroll
-                    for (int l = 0; l < 8; ++l) {
-                        const uint32_t kw = (uint32_t) *(const uint16_t *) (kb + 2 + 4 * l) | ((uint32_t) *(const uint16_t *) (kb + 4 + 4 * l) << 16);
-                        acc[l] = __builtin_fmaf(dd, (float) dot4((int) kw, (int) qq[8 * blk + l], 0), acc[l]);
-                    }
-                } else {
-                    // ggml_vec_dot_q4_0_q8_0 (AVX2): bytes_from_nibbles_32 puts the low nibbles at elements 0..15 and the high ones at 16..31, minus 8 each
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        const uint32_t kw = (uint32_t) *(const uint16_t *) (kb + 2 + 4 * l) | ((uint32_t) *(const uint16_t *) (kb + 4 + 4 * l) << 16);
-                        const int qlo = (int) qq[8 * blk + l], qhi = (int) qq[8 * blk + 4 + l];
-                        acc[l]     = __builtin_fmaf(dd, (float) (dot4((int) (kw & 0x0F0F0F0Fu), qlo, 0) - 8 * dot4(0x01010101, qlo, 0)), acc[l]);
-                        acc[l + 4] = __builtin_fmaf(dd, (float) (dot4((int) ((kw >> 4) & 0x0F0F0F0Fu), qhi, 0) - 8 * dot4(0x01010101, qhi, 0)), acc[l + 4]);
-                    }
-                }
-            }
-            const float t0 = __fadd_rn(acc[0], acc[4]), t1 = __fadd_rn(acc[1], acc[5]), t2 = __fadd_rn(acc[2], acc[6]), t3 = __fadd_rn(acc[3], acc[7]);
-            s = __fadd_rn(__fadd_rn(t0, t2), __fadd_rn(t1, t3));              // hsum_float_8
+            if constexpr (KVT != MI355Q_T_BF16) s = fa_dot_q80<KVT>(k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3], qd, qq, nblk);     // (fa_quant.cuh)
             s = __fmul_rn(s, scale);
             if (softcap != 0.0f) s = softcap * tanhf(s);
             s = __fadd_rn(s, mv);
@@ -836,23 +787,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     }
     __syncthreads();
     // ---- online softmax in order: rescale factor and weight per position
-    if (wave == 0) {
-        const unsigned long long tab = PLAN_EXP2F_T[lane & 31];
-        float carry = -INFINITY;
-        for (int64_t j0 = 0; j0 < n_kv; j0 += 64) {
-            const int64_t j = j0 + lane;
-            const float sj = j < n_kv ? fq_s[j] : -INFINITY;
-            float x = sj;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const float o = __shfl_up(x, off, 64); if (lane >= off) x = fmaxf(x, o); }
-            float prev = __shfl_up(x, 1, 64);
-            prev = fmaxf(lane == 0 ? -INFINITY : prev, carry);
-            carry = fmaxf(carry, __shfl(x, 63, 64));
-            const bool live = sj != -INFINITY, newmax = live && sj > prev;
-            const float e = expf_libm(newmax ? __fsub_rn(prev, sj) : live ? __fsub_rn(sj, prev) : 0.0f, tab);
-            if (j < n_kv) { fq_s[j] = newmax ? 1.0f : live ? e : 0.0f; msv[j] = newmax ? e : 1.0f; }
-        }
-    }
+    if (wave == 0) fa_seq_weights(fq_s, msv, n_kv, lane, PLAN_EXP2F_T[lane & 31]);
     __syncthreads();
     // ---- V . P in an F32 accumulator, a thread per output dim
     if (KVT == MI355Q_T_BF16 && tid < DV) {
@@ -870,23 +805,8 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
         }
         *(float *) (d.data + tid * d.nb[0] + h * d.nb[1] + t * d.nb[2] + b * d.nb[3]) = __fmul_rn(acc, __fdiv_rn(1.0f, S));
     } else if (KVT != MI355Q_T_BF16 && tid < DV) {
-        const char * vb = v.data + hv * v.nb[2] + bv * v.nb[3] + BB * (tid >> 5);
-        const int e = tid & 31;
-        float acc = 0.0f, S = 0.0f;
-#pragma unroll 4
-        for (int64_t j = 0; j < n_kv; ++j) {
-            const float vs = fq_s[j], ms = msv[j];
-            if (vs != 0.0f || ms != 1.0f) {                                   // (uniform)
-                const char * blk = vb + j * v.nb[1];
-                int qv;
-                if constexpr (KVT == MI355Q_TYPE_Q8_0) qv = (int) *(const int8_t *) (blk + 2 + e);
-                else { const int byte = (int) *(const uint8_t *) (blk + 2 + (e & 15)); qv = ((e < 16 ? byte : byte >> 4) & 15) - 8; }
-                const float vv = __fmul_rn((float) qv, __half2float(*(const __half *) blk));     // dequantize_row_q8_0 / _q4_0
-                if (ms != 1.0f) acc = __fmul_rn(acc, ms);                     // ggml_vec_scale_f32
-                acc = __builtin_fmaf(vv, vs, acc);                            // ggml_vec_mad_f32
-                S = __fadd_rn(__fmul_rn(S, ms), vs);
-            }
-        }
+        float acc, S;
+        if constexpr (KVT != MI355Q_T_BF16) fa_pv_q80<KVT>(v.data + hv * v.nb[2] + bv * v.nb[3] + BB * (tid >> 5), v.nb[1], tid & 31, fq_s, msv, n_kv, acc, S);     // (fa_quant.cuh)
         *(float *) (d.data + tid * d.nb[0] + h * d.nb[1] + t * d.nb[2] + b * d.nb[3]) = __fmul_rn(acc, __fdiv_rn(1.0f, S));
     }
 }

@@ -32,6 +32,7 @@
 #include <mutex>
 
 #include "gemv_stream.cuh"
+#include "fa_quant.cuh"
 
 namespace mi355q {
 
@@ -39,7 +40,7 @@ constexpr int PLAN_D_MAX = 8;                     // ring depth (1-KiB steps in 
 __host__ __device__ constexpr int plan_depth(int type) {   // Q5_K / Q6_K slots carry qh too (1.5 KiB per step): 6 steps are the bytes of 8 Q4_K steps
     return (type == MI355Q_TYPE_Q5_K || type == MI355Q_TYPE_Q6_K) ? 6 : PLAN_D_MAX;
 }
-enum { PLAN_F_NEW_X = 2, PLAN_F_PLAIN_Y = 4, PLAN_F_SUM = 8, PLAN_F_SUM_PLAIN = 16, PLAN_F_PAIRED = 32, PLAN_F_DIRECT = 64, PLAN_F_ATTN_LDS = 128 };
+enum { PLAN_F_NEW_X = 2, PLAN_F_PLAIN_Y = 4, PLAN_F_SUM = 8, PLAN_F_SUM_PLAIN = 16, PLAN_F_PAIRED = 32, PLAN_F_DIRECT = 64, PLAN_F_ATTN_LDS = 128, PLAN_F_ATTN_Q = 256 };
 enum { PLAN_K_GEMV = 0, PLAN_K_ATTN = 1, PLAN_K_COMBINE = 2 };
 enum { PLAN_SYNC_ABORT = 0, PLAN_SYNC_WORDS = 32 };
 
@@ -62,6 +63,7 @@ struct AttnStage {
     int kv_lds;                                    // the split's K / V window fits the LDS: plan_attn_lds runs the stage
     int fa_seq;                                    // rows-per-position V cache, window in one workgroup: the CPU's sequential f16 accumulation (plan_attn_lds)
     int entry_barrier;                             // the previous stage is not a GEMV: its last LDS reads must be fenced off
+    int kv_type, kv_rb, kv_unit;                   // quantized cache (plan_attn_q80): MI355Q_TYPE_Q8_0 / _Q4_0 (0: f16), bytes per head row, bytes per copy unit (2, 4, 8)
     float scale;
     // rope (ggml_rope_cache_init; see ops_glue.hip k_rope)
     int n_dims, neox; float freq_scale, ext_factor, attn_factor, theta_scale, corr0, corr1;
@@ -1252,6 +1254,212 @@ static __device__ __noinline__ bool plan_attn_lds(AttnC a_in, const StageCtx & c
     return true;
 }
 
+// ---- attention of one token over a Q8_0 / Q4_0 cache, K / V window in LDS ----------------------------------------------------------------------
+// The flash layout only (rows per position).  Workgroup = (head h, KV split sp), as plan_attn_lds.  The per-position arithmetic is
+// k_flash_attn_ext_q80's (fa_quant.cuh, shared): q roped in f32 and quantized to Q8_0, scores by the CPU's block dot, the online softmax in position
+// order, V dequantized into an F32 accumulator.  This token's K / V rows are quantized with CPY f32 -> q8_0 / q4_0's arithmetic into the cache AND
+// into the LDS window, so that its own position is read back from the blocks as the CPU reads it.  One split: the output is k_flash_attn_ext_q80's,
+// bit for bit.  Several: each split publishes (its F32 accumulator, its maximum, its sum S) and plan_attn_combine merges them.
+//   0  polls of q / k / v | rope table and cache slot | window copy (2 x cnt rows of hd / 32 blocks: 2-, 4- or 8-byte units) and the mask
+//   1  rope of q and k in f32 (in place);  2  q -> Q8_0 (wave 0), this token's K row (wave 1) and V row (wave 2) -> blocks
+//   3  scores, one position per thread;  4  softmax walk (wave 0);  5  V . P, one thread per output dim;  publish
+template <typename T>
+__device__ __forceinline__ void plan_copy_rows(char * lds_dst, const char * src, int64_t nb, int rows, int rb, int wi, int n_w, int lane) {
+    const int U = rb / (int) sizeof(T);                                        // units per row
+    const int ipi = U >= 64 ? 1 : 64 / U, li = U >= 64 ? 0 : lane / U, lc = U >= 64 ? lane : lane - li * U;
+    if (li >= ipi) return;
+    const int step = n_w * ipi;
+    for (int cu = lc; cu < U; cu += 64) {
+        for (int r0 = wi * ipi + li; r0 < rows; r0 += 4 * step) {
+            T t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int r = r0 + u * step; if (r < rows) t[u] = *(const T *) (src + (int64_t) r * nb + (int64_t) cu * (int) sizeof(T)); }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int r = r0 + u * step; if (r < rows) *(T *) (lds_dst + r * rb + cu * (int) sizeof(T)) = t[u]; }
+        }
+    }
+}
+
+template <int KVT>
+static __device__ __noinline__ bool plan_attn_q80(AttnC a_in, const StageCtx & c_in, unsigned tag_in) {
+    constexpr int BB = kv_block_bytes<KVT>();
+    const AttnC a = (AttnC) (uintptr_t) uniform_ptr((const void *) (uintptr_t) a_in);
+    extern __shared__ __attribute__((aligned(16))) uint8_t plan_lds_attnq[];
+    StageCtx c;
+    c.image = __builtin_amdgcn_readfirstlane(c_in.image);
+    c.lds = plan_lds_attnq; c.ctl = (int *) (plan_lds_attnq + c.image); c.part = (double *) (plan_lds_attnq + c.image + 64);
+    c.stg = (float *) (plan_lds_attnq + c.image + 64 + 8 * GEMV_WAVES + 1024);
+    c.sync = uniform_ptr(c_in.sync); c.timeout = c_in.timeout;
+    c.grid = (unsigned) __builtin_amdgcn_readfirstlane((int) c_in.grid); c.epoch = (unsigned) __builtin_amdgcn_readfirstlane((int) c_in.epoch);
+    c.even = c_in.even; c.stage = __builtin_amdgcn_readfirstlane(c_in.stage);
+    c.next_desc = uniform_ptr(c_in.next_desc); c.next_attn = uniform_ptr(c_in.next_attn); c.next_desc2 = uniform_ptr(c_in.next_desc2); c.pre_lds = c_in.pre_lds;
+    const unsigned tag = (unsigned) __builtin_amdgcn_readfirstlane((int) tag_in);
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int tid = (int) threadIdx.x;
+    const int hd = a->hd, n_split = a->n_split;
+    if ((int) blockIdx.x >= a->n_head * n_split) return true;                    // (uniform)
+    const int h = (int) blockIdx.x / n_split, sp = (int) blockIdx.x % n_split, gq = a->n_head / a->n_head_kv, g = h / gq;
+    const int half = hd >> 1, per_pad = (a->per + 31) & ~31, rb = a->kv_rb, nblk = hd >> 5;
+    // LDS (inside the staging area; every area a multiple of 16 bytes)
+    float * misc = c.stg;                                                      // [16]: 0 maximum, 2 cache slot (int)
+    float * sq = misc + 16, * sk = sq + hd, * sv = sk + hd, * cst = sv + hd;   // q / k / v as polled (q, k roped in place) | cos [hd/2] sin [hd/2]
+    float * qd = cst + hd;                                                     // [8] q's block scales
+    uint32_t * qq = (uint32_t *) (qd + 8);                                     // [64] q's packed quants
+    float * sc = (float *) (qq + 64);                                          // [per_pad] mask -> scores -> weights
+    float * msv = sc + per_pad;                                                // [per_pad] rescale factors
+    char * kwin = (char *) (msv + per_pad);                                    // [cnt][rb] K blocks
+    char * vwin = kwin + (size_t) per_pad * rb;                                // [cnt][rb] V blocks
+    const int32_t * pos_p = a->pos, * nkv_p = a->n_kv_dev;
+    char * const * kdst_p = a->k_dst, * const * vdst_p = a->v_dst;
+    const int pos = pos_p[0];
+    char * const kdst = *kdst_p, * const vdst = *vdst_p;
+    int n_kv = a->n_kv;
+    if (nkv_p) n_kv = min(n_kv, max(1, nkv_p[0]));
+    const int per = (n_kv + n_split - 1) / n_split;
+    const int j0 = sp * per, j1 = min(n_kv, j0 + per), cnt = max(0, j1 - j0);
+    if (a->entry_barrier) plan_lds_barrier();
+    plan_prefetch_desc(c, wave, lane);
+    PLAN_STAMP(0);
+    unsigned long long exp_tab = 0ull;
+    if (wave == 0) exp_tab = PLAN_EXP2F_T[lane & 31];
+
+    // ---- 0. polls | rope table | window copy ----
+    const int nch = (hd + 127) >> 7, n_poll = 3 * nch, n_tab = (half + 63) >> 6;
+    if (wave < n_poll) {
+        PollCtx pc; pc.sync = c.sync; pc.timeout = c.timeout; pc.t0 = __builtin_amdgcn_s_memrealtime();
+        unsigned spins = 0;
+        const int which = wave / nch, ch = wave % nch;
+        VecSrc vs;
+        if (which == 0)      { vs.plain = a->q.plain; vs.gran = a->q.gran; vs.tag_off = a->q.tag_off; }
+        else if (which == 1) { vs.plain = a->k.plain; vs.gran = a->k.gran; vs.tag_off = a->k.tag_off; }
+        else                 { vs.plain = a->v.plain; vs.gran = a->v.gran; vs.tag_off = a->v.tag_off; }
+        vs.pad = 0;
+        const SrcView s = src_view(vs, (which == 0 ? h : g) * hd, hd, c.epoch);
+        float * dst = which == 0 ? sq : which == 1 ? sk : sv;
+        float v0 = 0.f, v1 = 0.f;
+        bool ok_all = true;
+        for (;;) {
+            const bool ok = src_try(s, ch, lane, v0, v1) || 128 * ch + 2 * lane >= hd;
+            if (__ballot(!ok) == 0ull) break;
+            if (!poll_backoff(pc, spins, lane)) { ok_all = false; break; }
+        }
+        const int e = 128 * ch + 2 * lane;
+        if (ok_all && e < hd) { dst[e] = v0; dst[e + 1] = v1; }
+        if (!ok_all && lane == 0) c.ctl[CTL_OK] = 0;
+    } else if (wave < n_poll + n_tab) {
+        // rope table: plan_attn_lds step 0's (ops_glue.hip k_rope / ggml-cpu/ops.cpp:5088-5270)
+        const int ip = 64 * (wave - n_poll) + lane;
+        const int n_dims = a->n_dims;
+        if (2 * ip < n_dims) {
+            const float * ffp = a->freq_factors;
+            const float ff = ffp ? ffp[ip] : 1.0f;
+            const float tscale = a->theta_scale;
+            float th = (float) pos;
+            const int steps = (n_dims >> 1) - 1;
+#pragma unroll 8
+            for (int j = 0; j < steps; ++j) th = __fmul_rn(th, j < ip ? tscale : 1.0f);
+            const float theta_extrap = __fdiv_rn(th, ff);
+            const float theta_interp = a->freq_scale * theta_extrap;
+            float theta = theta_interp, mscale = a->attn_factor;
+            if (a->ext_factor != 0.0f) {
+                const float y = ((float) ip - a->corr0) / fmaxf(0.001f, a->corr1 - a->corr0);
+                const float ramp_mix = (1.0f - fminf(1.0f, fmaxf(0.0f, y))) * a->ext_factor;
+                theta = theta_interp * (1.0f - ramp_mix) + theta_extrap * ramp_mix;
+                mscale *= 1.0f + 0.1f * logf(1.0f / a->freq_scale);
+            }
+            cst[ip] = cosf(theta) * mscale; cst[half + ip] = sinf(theta) * mscale;
+        }
+        if (wave == n_poll && lane == 0) {
+            const unsigned long long diff = (unsigned long long) (kdst - a->k_cache), np = (unsigned long long) a->k_nb_pos;
+            ((int *) misc)[2] = ((diff | np) >> 32) == 0ull ? (int) ((unsigned) diff / (unsigned) np) : (int) (diff / np);
+        }
+    } else {
+        const int wi = wave - n_poll - n_tab, n_w = GEMV_WAVES - n_poll - n_tab;
+        if (cnt > 0) {
+            const char * kb = a->k_cache + (int64_t) g * a->k_nb_head + (int64_t) j0 * a->k_nb_pos;
+            const char * vb = a->v_cache + (int64_t) g * a->v_nb_head + (int64_t) j0 * a->v_nb_pos;
+            const int64_t knp = a->k_nb_pos, vnp = a->v_nb_pos;
+            const int unit = a->kv_unit;
+            if (unit == 8)      { plan_copy_rows<uint2>(kwin, kb, knp, cnt, rb, wi, n_w, lane);    plan_copy_rows<uint2>(vwin, vb, vnp, cnt, rb, wi, n_w, lane); }
+            else if (unit == 4) { plan_copy_rows<uint32_t>(kwin, kb, knp, cnt, rb, wi, n_w, lane); plan_copy_rows<uint32_t>(vwin, vb, vnp, cnt, rb, wi, n_w, lane); }
+            else                { plan_copy_rows<uint16_t>(kwin, kb, knp, cnt, rb, wi, n_w, lane); plan_copy_rows<uint16_t>(vwin, vb, vnp, cnt, rb, wi, n_w, lane); }
+        }
+        const char * maskp = a->mask; const int mask_f16 = a->mask_f16;
+        for (int jj = wi * 64 + lane; jj < cnt; jj += n_w * 64)
+            sc[jj] = maskp ? (mask_f16 ? __half2float(((const __half *) maskp)[j0 + jj]) : ((const float *) maskp)[j0 + jj]) : 0.0f;
+    }
+    const int n_dims_r = a->n_dims, neox_r = a->neox, plain_out = a->plain;
+    const float scale_r = a->scale;
+    Granule * const out_gran = a->out_gran, * const part_gran = a->part; float * const out_plain = a->out_plain;
+    asm volatile("" :: "s"(n_dims_r), "s"(neox_r), "s"(plain_out), "s"(scale_r), "s"(out_gran), "s"(part_gran), "s"(out_plain));
+    plan_lds_barrier();
+    if (!c.ctl[CTL_OK]) return false;
+    PLAN_STAMP(1);
+
+    // ---- 1. rope of q and k in f32, in place (a thread owns one rotated pair) ----
+    if (tid < hd) {
+        const bool isq = tid < half;
+        float * x = isq ? sq : sk;
+        const int ip = isq ? tid : tid - half, i0 = 2 * ip;
+        if (i0 < n_dims_r) {
+            const float cs = cst[ip], sn = cst[half + ip];
+            const int e0 = neox_r ? ip : i0, e1 = neox_r ? ip + n_dims_r / 2 : i0 + 1;
+            const float x0 = x[e0], x1 = x[e1];
+            x[e0] = x0 * cs - x1 * sn; x[e1] = x0 * sn + x1 * cs;
+        }
+    }
+    plan_lds_barrier();
+    // ---- 2. q -> Q8_0 for the scores; this token's K / V rows -> blocks: into the cache (one workgroup per kv head) and into the window ----
+    const int slot = ((const int *) misc)[2];
+    const bool in_win = slot >= j0 && slot < j1, store = sp == 0 && h % gq == 0;
+    if (wave == 0) fa_quantize_q(sq, lane, hd, qq, qd);
+    else if (wave == 1 || wave == 2) {
+        const float * x = wave == 1 ? sk : sv;
+        const int e = 4 * lane;
+        const float4 v4 = e < hd ? make_float4(x[e], x[e + 1], x[e + 2], x[e + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        uint32_t w; float d;
+        kv_quant_group8<KVT>(v4, w, d);
+        if (e < hd) {
+            const int off = BB * (lane >> 3), l8 = lane & 7;
+            if (in_win) kv_store_group8<KVT>((wave == 1 ? kwin : vwin) + (size_t) (slot - j0) * rb + off, l8, w, d);
+            if (store)  kv_store_group8<KVT>((wave == 1 ? kdst : vdst) + (int64_t) g * rb + off, l8, w, d);
+        }
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(2);
+    // ---- 3. scores: one position per thread (a masked position stays -inf whatever its cache blocks hold) ----
+    for (int jj = tid; jj < cnt; jj += GEMV_THREADS) {
+        const float m = sc[jj];
+        sc[jj] = m == -INFINITY ? -INFINITY : __fadd_rn(__fmul_rn(fa_dot_q80<KVT>(kwin + (size_t) jj * rb, qd, qq, nblk), scale_r), m);
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(3);
+    // ---- 4. the online softmax in position order ----
+    if (wave == 0) {
+        const float mx = fa_seq_weights(sc, msv, cnt, lane, exp_tab);
+        if (lane == 0) misc[0] = mx;
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(4);
+    // ---- 5. V . P into the F32 accumulator; publish ----
+    if (tid < hd) {
+        float acc, S;
+        fa_pv_q80<KVT>(vwin + BB * (tid >> 5), rb, tid & 31, sc, msv, cnt, acc, S);
+        if (n_split == 1) {
+            const float r = __fmul_rn(acc, __fdiv_rn(1.0f, S));
+            publish(out_gran + h * hd + tid, r, tag);
+            if (plain_out) out_plain[h * hd + tid] = r;
+        } else {
+            Granule * part = part_gran + (size_t) ((size_t) h * n_split + sp) * (hd + 2);
+            publish(part + tid, acc, tag);
+            if (tid == 0) { publish(part + hd, misc[0], tag); publish(part + hd + 1, S, tag); }
+        }
+    }
+    PLAN_STAMP(5);
+    return true;
+}
+
 // merge the KV splits of a head: out = sum_s e^{m_s - M} o_s / sum_s e^{m_s - M} l_s     (workgroup h * n_split does head h)
 static __device__ __noinline__ bool plan_attn_combine(AttnC a_in, const StageCtx & c_in, unsigned tag_in) {
     const AttnC a = (AttnC) (uintptr_t) uniform_ptr((const void *) (uintptr_t) a_in);
@@ -1363,7 +1571,11 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
             default: break;
             }
         } else if (kind == PLAN_K_ATTN) {
-            ok = (st->flags & PLAN_F_ATTN_LDS) ? plan_attn_lds((AttnC) st->attn, c, epoch + st->tag_off) : plan_attn((AttnC) st->attn, c, epoch + st->tag_off);
+            const int af = st->flags;
+            if (af & PLAN_F_ATTN_Q)
+                ok = ((AttnC) st->attn)->kv_type == MI355Q_TYPE_Q8_0 ? plan_attn_q80<MI355Q_TYPE_Q8_0>((AttnC) st->attn, c, epoch + st->tag_off)
+                                                                     : plan_attn_q80<MI355Q_TYPE_Q4_0>((AttnC) st->attn, c, epoch + st->tag_off);
+            else ok = (af & PLAN_F_ATTN_LDS) ? plan_attn_lds((AttnC) st->attn, c, epoch + st->tag_off) : plan_attn((AttnC) st->attn, c, epoch + st->tag_off);
         } else {
             ok = plan_attn_combine((AttnC) st->attn, c, epoch + st->tag_off);
         }
@@ -1492,7 +1704,11 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             if (at->n_head < 1 || at->n_head_kv < 1 || at->n_head % at->n_head_kv || at->head_dim < 32 || at->head_dim > 256 || at->head_dim % 32 || at->n_kv < 1) { mi355q_set_error("plan_create: attn stage: bad head geometry"); return MI355Q_ERR_SHAPE; }
             if (at->rope.mode != 0 && at->rope.mode != 2) { mi355q_set_error("plan_create: attn stage: rope mode must be 0 or 2"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->rope.n_dims <= 0 || at->rope.n_dims % 2 || at->rope.n_dims > at->head_dim) { mi355q_set_error("plan_create: attn stage: rope n_dims"); return MI355Q_ERR_SHAPE; }
-            if (at->v_nb_dim != 2 && at->v_nb_pos != 2) { mi355q_set_error("plan_create: attn stage: V cache must be contiguous along head_dim or along positions"); return MI355Q_ERR_UNSUPPORTED; }
+            const int kvq = in.flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0);
+            if (kvq == (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0)) { mi355q_set_error("plan_create: attn stage: KV_Q8_0 and KV_Q4_0 both set"); return MI355Q_ERR_UNSUPPORTED; }
+            const int kv_bb = kvq == MI355Q_STAGE_KV_Q8_0 ? 34 : 18;
+            if (kvq && at->v_nb_dim != kv_bb) { mi355q_set_error("plan_create: attn stage: a q8_0 / q4_0 cache needs the flash layout (V rows per position, v_nb_dim = block bytes); the transposed V cache is not supported"); return MI355Q_ERR_UNSUPPORTED; }
+            if (!kvq && at->v_nb_dim != 2 && at->v_nb_pos != 2) { mi355q_set_error("plan_create: attn stage: V cache must be contiguous along head_dim or along positions"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->n_head > n_cu) { mi355q_set_error("plan_create: attn stage: more heads than CUs"); return MI355Q_ERR_UNSUPPORTED; }
             AttnStage A = {};
             const int hd = at->head_dim;
@@ -1501,6 +1717,13 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             A.k_nb_pos = at->k_nb_pos; A.k_nb_head = at->k_nb_head; A.v_nb_pos = at->v_nb_pos; A.v_nb_dim = at->v_nb_dim; A.v_nb_head = at->v_nb_head; A.v_dst_nb = at->v_dst_nb;
             A.k_dst = (char * const *) at->k_dst; A.v_dst = (char * const *) at->v_dst; A.mask = (const char *) at->mask; A.mask_f16 = at->mask_f16;
             A.n_head = at->n_head; A.n_head_kv = at->n_head_kv; A.hd = hd; A.n_kv = at->n_kv; A.scale = at->scale;
+            if (kvq) {                                         // a quantized cache: rows of hd / 32 blocks, copied into LDS in the widest unit every address allows
+                A.kv_type = kvq == MI355Q_STAGE_KV_Q8_0 ? MI355Q_TYPE_Q8_0 : MI355Q_TYPE_Q4_0; A.kv_rb = hd / 32 * kv_bb;
+                const uint64_t any = (uint64_t) (uintptr_t) at->k_cache | (uint64_t) (uintptr_t) at->v_cache | (uint64_t) at->k_nb_pos | (uint64_t) at->k_nb_head |
+                                     (uint64_t) at->v_nb_pos | (uint64_t) at->v_nb_head | (uint64_t) A.kv_rb;
+                A.kv_unit = (any & 7) == 0 ? 8 : (any & 3) == 0 ? 4 : 2;
+                if (any & 1) { mi355q_set_error("plan_create: attn stage: q8_0 / q4_0 cache addresses and strides must be even"); return MI355Q_ERR_UNSUPPORTED; }
+            }
             // KV splits per head: one workgroup per 256 positions, at most #CU / n_head.  A window of <= 256 positions is ONE workgroup per head and
             // needs no merge stage (a dependent hop costs more than reading 256 cache rows).
             A.n_split = (at->n_kv + 255) / 256; if (A.n_split > n_cu / at->n_head) A.n_split = n_cu / at->n_head; if (A.n_split < 1) A.n_split = 1;
@@ -1533,7 +1756,7 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             const size_t need2 = (size_t) 4 * A.n_split * (hd + 2) + 64;
             if (need > stg_max) stg_max = need;
             if (need2 > stg_max) stg_max = need2;
-            bytes += (int64_t) 2 * at->n_kv * at->n_head_kv * hd * 2;
+            bytes += (int64_t) 2 * at->n_kv * at->n_head_kv * (kvq ? A.kv_rb / hd : 2) * hd;
             continue;
         }
         if (in.kind != MI355Q_STAGE_GEMV) { mi355q_set_error("plan_create: unknown stage kind"); return MI355Q_ERR_UNSUPPORTED; }
@@ -1663,6 +1886,23 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             if (v[si].kind != PLAN_K_ATTN) continue;
             AttnStage & A = va[attn_of[si]];
             const int per_pad = (A.per + 31) & ~31;
+            A.entry_barrier = si == 0 || v[si - 1].kind != PLAN_K_GEMV;
+            if (A.kv_type) {
+                // a quantized cache always runs from LDS (plan_attn_q80): 21 hd + 352 bytes of vectors, 8 bytes of scores per position and the K / V
+                // windows of 2 x rb bytes per position (rb = hd / 32 x 34 or 18).  A window beyond that is refused: the caller falls back to the node ops.
+                const size_t need = (size_t) 4 * (16 + 4 * A.hd + 72) + (size_t) 8 * per_pad + (size_t) 2 * per_pad * A.kv_rb + 64;
+                if (fixed + ((std::max(need, stg_max) + 15) & ~(size_t) 15) > cap) {
+                    const size_t room = cap - fixed - 64 - (size_t) 4 * (16 + 4 * A.hd + 72);
+                    char msg[200];
+                    snprintf(msg, sizeof(msg), "plan_create: attn stage: a %s KV window of %d positions per split (%d split(s)) does not fit the LDS: at most %zu positions per split",
+                             A.kv_type == MI355Q_TYPE_Q8_0 ? "q8_0" : "q4_0", A.per, A.n_split, (room / (8 + 2 * (size_t) A.kv_rb)) & ~(size_t) 31);
+                    mi355q_set_error(msg);
+                    return MI355Q_ERR_UNSUPPORTED;
+                }
+                v[si].flags |= PLAN_F_ATTN_Q; if (need > stg_max) stg_max = need;
+                if (getenv("MI355Q_PLAN_VERBOSE")) fprintf(stderr, "mi355q plan: attention stage %zu: n_kv %d, %d split(s) of %d positions, %s cache, window in LDS (%zu bytes, %zu fixed, %d-byte copies)\n", si, A.n_kv, A.n_split, A.per, A.kv_type == MI355Q_TYPE_Q8_0 ? "q8_0" : "q4_0", need, fixed, A.kv_unit);
+                continue;
+            }
             const size_t need = (size_t) 50 * A.hd + 64 + (size_t) 8 * per_pad + (size_t) 4 * per_pad * A.hd + (size_t) 16 * per_pad + 64;     // (plan_attn_lds: 12.5 hd + 16 + 2 per floats, K rows of hd + 8 f16, V)
             const bool aligned = (A.k_nb_pos & 15) == 0 && (A.k_nb_head & 15) == 0 && ((uintptr_t) A.k_cache & 15) == 0 && ((uintptr_t) A.v_cache & 15) == 0 && (A.v_nb_head & 15) == 0 &&
                                  (A.v_nb_dim == 2 ? (A.v_nb_pos & 15) == 0 : (A.v_nb_dim & 15) == 0 && A.v_nb_pos == 2);

@@ -36,6 +36,11 @@ namespace { struct Handle { int ring; mi355q_plan * impl; }; }
 int mi355q_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int n_stages, int flags) {
     if (!out) { mi355q_set_error("plan_create: null argument"); return MI355Q_ERR_SHAPE; }
     static const int want_ring = [] { const char * e = getenv("MI355Q_PLAN_ENGINE"); return e && strcmp(e, "ring") == 0 ? 1 : 0; }();
+    if (want_ring && stages)                                   // plan_ring.hip has no quantized-cache attention stage: it would read the blocks as f16
+        for (int i = 0; i < n_stages; ++i)
+            if (stages[i].kind == MI355Q_STAGE_ATTN && (stages[i].flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0))) {
+                mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for a q8_0 / q4_0 KV cache"); return MI355Q_ERR_UNSUPPORTED;
+            }
     mi355q_plan * impl = nullptr;
     const int rc = want_ring ? mi355q_ring_plan_create(&impl, stages, n_stages, flags) : mi355q_regs_plan_create(&impl, stages, n_stages, flags);
     if (rc != MI355Q_OK) return rc;

@@ -302,6 +302,9 @@ def mul_mat_multi(ws_: list, x, outs=None, flags: int = 0):
     return ys
 
 
+_STAGE_KV = {"f16": 0, "q8_0": 0x4, "q4_0": 0x8}           # mi355q_stage.flags of an ATTN stage: MI355Q_STAGE_KV_Q8_0 / MI355Q_STAGE_KV_Q4_0
+
+
 class Plan:
     """A token's dependent chain as ONE persistent launch (mi355q_plan_*).
 
@@ -313,7 +316,8 @@ class Plan:
       * dict(attn=dict(q=, k=, v=, pos=, rope=dict(n_dims=, mode=0, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0,
                        attn_factor=1.0, beta_fast=32.0, beta_slow=1.0), freq_factors=None, k_cache=, v_cache=, k_nb_pos=, k_nb_head=, v_nb_pos=,
                        v_nb_dim=, v_nb_head=, k_dst=, v_dst= (int64 device tensors holding the destination ADDRESSES), v_dst_nb=, mask=None,
-                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=), no_plain=False)                 -- see include/mi355q.h mi355q_attn.
+                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16"), no_plain=False)       -- see include/mi355q.h mi355q_attn;
+        kv="q8_0" / "q4_0": the caches hold blocks of that type (uint8 tensors; MI355Q_STAGE_KV_Q8_0 / _Q4_0, flash layout only).
     The tensors are referenced by address: keep them alive (the Plan holds references) and do not move them."""
 
     def __init__(self, stages, flags: int = 0):
@@ -336,6 +340,10 @@ class Plan:
                 at.mask_f16 = 1 if (a.get("mask") is not None and a["mask"].dtype == torch.float16) else 0
                 at.scale = float(a["scale"])
                 st.kind = STAGE_ATTN; st.attn = C.pointer(at); st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
+                kv = a.get("kv", "f16")
+                if kv not in _STAGE_KV:
+                    raise ValueError(f"attn kv must be one of {sorted(_STAGE_KV)}, not {kv!r}")
+                st.flags |= _STAGE_KV[kv]
                 self._keep.append((a, at))
             else:
                 if isinstance(sd, dict):
@@ -498,12 +506,12 @@ def op_cpy(a, out, kv: str = "q8_0"):
     return out
 
 
-def op_cpy_indirect(a, out, table, index: int):
+def op_cpy_indirect(a, out, table, index: int, kv: str = "q8_0"):
     """GGML_OP_CPY into a destination resolved on the device: `out` gives the type, shape and strides, and the data pointer is read from
     table[index] (`table`: a device int64 tensor of addresses) when the kernel runs -- the KV store of a replayed launch graph."""
     torch = _torch()
     assert table.dtype == torch.int64 and table.is_cuda and 0 <= index < table.numel()
-    td_out = _td_q8_0(out) if out.dtype == torch.uint8 else _td(out)
+    td_out = _td_q8_0(out, kv) if out.dtype == torch.uint8 else _td(out)
     _check(lib().mi355q_op_cpy_indirect(C.byref(_td(a)), C.byref(td_out), table.data_ptr(), index, _stream(torch)), "op_cpy_indirect")
     return out
 
