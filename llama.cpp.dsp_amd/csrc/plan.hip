@@ -98,8 +98,14 @@ constexpr unsigned SET_ALL  = SET_K456 | SET_80;
 // IQ4_XS / IQ4_NL models (llama-quant.cpp: IQ4_XS or IQ4_NL for most tensors, Q5_K / Q6_K for attn_v, some ffn_down and the output matrix)
 constexpr unsigned SET_IQ4  = tbit(MI355Q_TYPE_IQ4_XS) | tbit(MI355Q_TYPE_IQ4_NL) | tbit(MI355Q_TYPE_Q5_K) | tbit(MI355Q_TYPE_Q6_K);
 constexpr unsigned SET_ANY  = SET_ALL | SET_IQ4;
+// a GEMV stage whose rows end in a partial step (row_chunks % 64 != 0) needs the row loop with the per-lane tail test; every other plan (every
+// Llama K: 4096, 8192, 14336, 28672) gets the kernel without it.  Not a weight type: the high bit of the set.
+constexpr unsigned SET_TAIL = 1u << 31;
 
-struct PlanCursor { int gr, s; const uint8_t * row; };
+// The loader's position: row gr of the stage, step s of it.  `row` is the row being requested; `alt` the row the wave takes after it, so a row
+// switch is a move and one 64-bit add instead of StageW::row_ptr's matrix select and multiply (plan_advance).  Rows [gr, bound) lie in one
+// matrix; crossing `bound` (the next matrix's first row) re-seeks through row_ptr.
+struct PlanCursor { int gr, s, bound; const uint8_t * row, * alt; int64_t adv0, adv1; };
 
 #ifdef MI355Q_STAMPS
 // Diagnostic build only (libmi355q_dbg.so): waves 0 and 15 of every workgroup record 100 MHz wall-clock stamps per stage:
@@ -147,6 +153,25 @@ struct StageW {
         const int rb = mi == 0 ? 0 : mi == 1 ? b1 : mi == 2 ? b2 : b3;
         return (const uint8_t *) (w + (uint64_t) ((int64_t) (r - rb) * ws));
     }
+    // the loader's cursor at local row r (the first row of the wave, or the first row it takes in a new matrix).  adv0 / adv1: what the next
+    // row of the wave lies past the current one when the current row is even / odd -- one 16-row stride of its matrix; a PAIRED stage
+    // alternates matrices, so there `alt` holds the other matrix's row of the pair and the stride is that of the matrix just left.
+    __device__ __forceinline__ void seek(PlanCursor & ld, int r) const {       // (not PAIRED)
+        const uint64_t a0 = (uint64_t) w0, a1 = (uint64_t) w1, a2 = (uint64_t) w2, a3 = (uint64_t) w3;
+        const int64_t s0 = ws0, s1 = ws1, s2 = ws2, s3 = ws3;
+        const int b1 = rb1, b2 = rb2, b3 = rb3;
+        const int mi = (r >= b1) + (r >= b2) + (r >= b3);
+        const uint64_t w = mi == 0 ? a0 : mi == 1 ? a1 : mi == 2 ? a2 : a3;
+        const int64_t ws = mi == 0 ? s0 : mi == 1 ? s1 : mi == 2 ? s2 : s3;
+        const int rb = mi == 0 ? 0 : mi == 1 ? b1 : mi == 2 ? b2 : b3;
+        ld.row = (const uint8_t *) (w + (uint64_t) ((int64_t) (r - rb) * ws));
+        ld.adv0 = ld.adv1 = GEMV_WAVES * ws; ld.alt = ld.row + ld.adv0;
+        ld.bound = mi == 0 ? b1 : mi == 1 ? b2 : mi == 2 ? b3 : 0x7FFFFFFF;
+    }
+    __device__ __forceinline__ void seek_first(PlanCursor & ld, int r) const {  // a wave's first row (PAIRED: even, the matrix-0 row of its first pair)
+        if (!paired) { seek(ld, r); return; }
+        ld.row = row_ptr(r); ld.alt = row_ptr(r + 1); ld.adv0 = GEMV_WAVES * ws0; ld.adv1 = GEMV_WAVES * ws1; ld.bound = 0x7FFFFFFF;
+    }
     __device__ __forceinline__ float * y_ptr(int r) const {
         const uint64_t a0 = (uint64_t) y0, a1 = (uint64_t) y1, a2 = (uint64_t) y2, a3 = (uint64_t) y3;
         const int b1 = rb1, b2 = rb2, b3 = rb3;
@@ -169,19 +194,31 @@ template <int T> __device__ __forceinline__ StageGeom plan_geom(int k, int r_hi)
 // the row a wave takes after local row r: rows are dealt round robin; a PAIRED stage deals PAIRS (rows 2q, 2q+1 back to back, then 16 pairs on)
 __device__ __forceinline__ int plan_next_row(int r, int paired) { return r + (paired ? ((r & 1) ? 2 * GEMV_WAVES - 1 : 1) : GEMV_WAVES); }
 
-template <int T>
+// the loader's next row: the row already resolved in `alt` becomes current, and `alt` moves one row of the wave further -- along its own
+// matrix, or (PAIRED) from the row just left along that one's (see StageW::seek)
+__device__ __forceinline__ void plan_advance(PlanCursor & ld, const StageW & st, int r_hi) {
+    const int gr = ld.gr;
+    const uint8_t * const left = ld.row;
+    ld.gr = plan_next_row(gr, st.paired);
+    ld.row = ld.alt;
+    ld.alt = (st.paired ? left : ld.alt) + ((gr & 1) ? ld.adv1 : ld.adv0);
+    if (ld.gr >= ld.bound && ld.gr < r_hi) st.seek(ld, ld.gr);
+}
+
+// NOTAIL: every step of a row is 64 whole chunks (nchunks % 64 == 0: every Llama K) -- no per-lane tail test
+template <int T, bool NOTAIL>
 __device__ __forceinline__ void plan_issue(Chunk & slot, PlanCursor & ld, const StageW & st, const StageGeom & g, int lane) {
     if (ld.gr < g.r_hi) {                                     // wave-uniform
-        if (64 * ld.s + lane < g.nchunks) chunk_load<T>(slot, ld.row, g.nb, ld.s, lane);
-        if (++ld.s == g.steps) { ld.s = 0; ld.gr = plan_next_row(ld.gr, st.paired); if (ld.gr < g.r_hi) ld.row = st.row_ptr(ld.gr); }
+        if (NOTAIL || 64 * ld.s + lane < g.nchunks) chunk_load<T>(slot, ld.row, g.nb, ld.s, lane);
+        if (++ld.s == g.steps) { ld.s = 0; plan_advance(ld, st, g.r_hi); }
     }
 }
 
 // request slots [from, to) of the ring for stage st (its loader cursor continues where it stands)
-template <int T, int D>
+template <int T, int D, bool NOTAIL>
 __device__ __forceinline__ void plan_fill(Chunk (&ring)[D], int from, int to, PlanCursor & ld, const StageW & st, const StageGeom & g, int lane) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) if (d >= from && d < to) plan_issue<T>(ring[d], ld, st, g, lane);
+    for (int d = 0; d < D; ++d) if (d >= from && d < to) plan_issue<T, NOTAIL>(ring[d], ld, st, g, lane);
 }
 
 __device__ __forceinline__ void publish(Granule * gp, float v, unsigned tag) {
@@ -191,7 +228,7 @@ __device__ __forceinline__ void publish(Granule * gp, float v, unsigned tag) {
 __device__ __forceinline__ float unary_f(int uop, float x);
 
 // consume this wave's rows of the stage; slot d holds item d, d+D, ... ; refills keep D items in flight
-template <int T, int D>
+template <int T, int D, bool NOTAIL>
 __device__ __forceinline__ void plan_run(Chunk (&ring)[D], PlanCursor & ld, const StageW & st, const StageGeom & g, int r_lo, int wave, int lane,
                                          const ActView * av, unsigned tag, bool plain, int pair_p0, int pair_unary) {
     // the consumers' lane-invariant state (LDS offsets, shifts) is derived from an opaque copy of the lane id HERE, so
@@ -204,7 +241,7 @@ __device__ __forceinline__ void plan_run(Chunk (&ring)[D], PlanCursor & ld, cons
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (cs_gr < g.r_hi) {                             // wave-uniform
-                if (64 * cs_s + lane_c < g.nchunks) Consume<T, 1>::run(ring[d], cs_s, lane_c, av, acc);
+                if (NOTAIL || 64 * cs_s + lane_c < g.nchunks) Consume<T, 1>::run(ring[d], cs_s, lane_c, av, acc);
                 if (++cs_s == g.steps) {                      // row finished: reduce, publish (one granule), next row
                     const float t = wave_sum(acc[0]);
                     if (st.paired) {                           // (wave-uniform)
@@ -217,7 +254,7 @@ __device__ __forceinline__ void plan_run(Chunk (&ring)[D], PlanCursor & ld, cons
                     } else if (lane_c == 0) { publish(st.g + cs_gr, t, tag); if (plain) *st.y_ptr(cs_gr) = t; }
                     acc[0] = 0.0f; cs_s = 0; cs_gr = plan_next_row(cs_gr, st.paired);
                 }
-                plan_issue<T>(ring[d], ld, st, g, lane);      // refill the slot just consumed
+                plan_issue<T, NOTAIL>(ring[d], ld, st, g, lane);   // refill the slot just consumed
             }
         }
     }
@@ -455,7 +492,7 @@ __device__ __forceinline__ bool plan_gather_direct(StageC st, const StageCtx & c
 
 // One GEMV stage, start to finish, for weight type T:
 //   prime (weights in flight) -> [gather x (polls its producers) -> glue -> quantize x -> LDS] -> stream rows, publishing every y
-template <int T>
+template <int T, bool NOTAIL>
 static __device__ __forceinline__ bool plan_stage(StageC st, const StageCtx & c) {
     // an opaque copy of the lane id per stage: everything derived from it is recomputed here (a few VALU ops) instead
     // of being hoisted out of the stage loop for BOTH types' loaders, quantizers and pollers and kept live (and spilled)
@@ -477,13 +514,13 @@ static __device__ __forceinline__ bool plan_stage(StageC st, const StageCtx & c)
     constexpr int PLAN_D = plan_depth(T);
     Chunk ring[PLAN_D];
     PlanCursor ld;
-    ld.gr = r_lo + (sw.paired ? 2 * wave : wave); ld.s = 0; ld.row = nullptr;
-    if (ld.gr < r_hi) ld.row = sw.row_ptr(ld.gr);
+    ld.gr = r_lo + (sw.paired ? 2 * wave : wave); ld.s = 0; ld.row = ld.alt = nullptr; ld.adv0 = ld.adv1 = 0; ld.bound = 0x7FFFFFFF;
+    if (ld.gr < r_hi) sw.seek_first(ld, ld.gr);
 #ifdef MI355Q_STAMPS
     { unsigned long long probe = (unsigned long long) (uintptr_t) ld.row + (unsigned) k; asm volatile("" :: "s"(probe)); }   // (forces the descriptor's scalar loads to have returned)
     PLAN_STAMP(5);
 #endif
-    plan_fill<T, PLAN_D>(ring, 0, st->prime, ld, sw, g, lane);                 // weights start flowing before anything else
+    plan_fill<T, PLAN_D, NOTAIL>(ring, 0, st->prime, ld, sw, g, lane);         // weights start flowing before anything else
     plan_prefetch_desc(c, wave, lane);
     PLAN_STAMP(1);
 
@@ -542,14 +579,14 @@ static __device__ __forceinline__ bool plan_stage(StageC st, const StageCtx & c)
         plan_lds_barrier();
         }
     }
-    plan_fill<T, PLAN_D>(ring, st->prime, PLAN_D, ld, sw, g, lane);                // top the ring up (a no-op when prime == depth)
+    plan_fill<T, PLAN_D, NOTAIL>(ring, st->prime, PLAN_D, ld, sw, g, lane);        // top the ring up (a no-op when prime == depth)
     sw.load_out(st);
     PLAN_STAMP(3);
     ActView av[1];
     av[0].base = c.lds; av[0].k = k;
     // (a PAIRED stage publishes unary(row of matrix 0) * (row of matrix 1) per pair from the wave that streamed both: the output unary is kept in
     // the high byte of x_unary)
-    plan_run<T, PLAN_D>(ring, ld, sw, g, r_lo, wave, lane, av, c.epoch + st->tag_off, (flags & PLAN_F_PLAIN_Y) != 0, pair_p0, st->x_unary >> 8);
+    plan_run<T, PLAN_D, NOTAIL>(ring, ld, sw, g, r_lo, wave, lane, av, c.epoch + st->tag_off, (flags & PLAN_F_PLAIN_Y) != 0, pair_p0, st->x_unary >> 8);
     PLAN_STAMP(4);
     return true;
 }
@@ -1525,6 +1562,7 @@ static __device__ __noinline__ bool plan_attn_combine(AttnC a_in, const StageCtx
 template <unsigned SET>
 __global__ void __launch_bounds__(GEMV_THREADS)
 k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsigned long long timeout_ticks, int lds_image_bytes, unsigned epoch) {
+    constexpr bool NOTAIL = (SET & SET_TAIL) == 0;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     StageC stages = (StageC) stages_g;
     if (__hip_atomic_load(sync + PLAN_SYNC_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;   // sticky: a plan that timed out stays dead
@@ -1561,13 +1599,13 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
         const int kind = st->kind;
         if (kind == PLAN_K_GEMV) {
             switch (st->type) {
-            case MI355Q_TYPE_Q4_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q4_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q4_K>(st, c); break;
-            case MI355Q_TYPE_Q5_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q5_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q5_K>(st, c); break;
-            case MI355Q_TYPE_Q6_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q6_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q6_K>(st, c); break;
-            case MI355Q_TYPE_Q8_0: if constexpr ((SET & tbit(MI355Q_TYPE_Q8_0)) != 0) ok = plan_stage<MI355Q_TYPE_Q8_0>(st, c); break;
-            case MI355Q_TYPE_Q4_0: if constexpr ((SET & tbit(MI355Q_TYPE_Q4_0)) != 0) ok = plan_stage<MI355Q_TYPE_Q4_0>(st, c); break;
-            case MI355Q_TYPE_IQ4_NL: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_NL)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_NL>(st, c); break;
-            case MI355Q_TYPE_IQ4_XS: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_XS)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_XS>(st, c); break;
+            case MI355Q_TYPE_Q4_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q4_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q4_K, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_Q5_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q5_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q5_K, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_Q6_K: if constexpr ((SET & tbit(MI355Q_TYPE_Q6_K)) != 0) ok = plan_stage<MI355Q_TYPE_Q6_K, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_Q8_0: if constexpr ((SET & tbit(MI355Q_TYPE_Q8_0)) != 0) ok = plan_stage<MI355Q_TYPE_Q8_0, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_Q4_0: if constexpr ((SET & tbit(MI355Q_TYPE_Q4_0)) != 0) ok = plan_stage<MI355Q_TYPE_Q4_0, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_IQ4_NL: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_NL)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_NL, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_IQ4_XS: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_XS)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_XS, NOTAIL>(st, c); break;
             default: break;
             }
         } else if (kind == PLAN_K_ATTN) {
@@ -1624,13 +1662,16 @@ static void plan_block_give(int dev, unsigned char * p, size_t bytes) {
     (void) hipFree(p);
 }
 
-static const void * plan_kernel(unsigned set) {
-    if ((set & ~SET_K46) == 0)  return (const void *) k_plan<SET_K46>;
-    if ((set & ~SET_K456) == 0) return (const void *) k_plan<SET_K456>;
-    if ((set & ~SET_80) == 0)   return (const void *) k_plan<SET_80>;
-    if ((set & ~SET_ALL) == 0)  return (const void *) k_plan<SET_ALL>;
-    if ((set & ~SET_IQ4) == 0)  return (const void *) k_plan<SET_IQ4>;
+template <unsigned TAIL> static const void * plan_kernel_t(unsigned set) {
+    if ((set & ~SET_K46) == 0)  return (const void *) k_plan<SET_K46 | TAIL>;
+    if ((set & ~SET_K456) == 0) return (const void *) k_plan<SET_K456 | TAIL>;
+    if ((set & ~SET_80) == 0)   return (const void *) k_plan<SET_80 | TAIL>;
+    if ((set & ~SET_ALL) == 0)  return (const void *) k_plan<SET_ALL | TAIL>;
+    if ((set & ~SET_IQ4) == 0)  return (const void *) k_plan<SET_IQ4 | TAIL>;
     return nullptr;                                            // (a mix of the IQ4 types with Q4_K / Q8_0 / Q4_0: no instantiation)
+}
+static const void * plan_kernel(unsigned set) {
+    return (set & SET_TAIL) ? plan_kernel_t<SET_TAIL>(set & ~SET_TAIL) : plan_kernel_t<0>(set);
 }
 
 #ifdef MI355Q_STAMPS
@@ -1835,7 +1876,7 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             p.wg_base = 0; p.wg_count = n_cu; p.group = 1; p.pub_wg = (int) (v.size() % (size_t) n_cu);
             p.prime = plan_depth(type);
             v.push_back(p); attn_of.push_back(-1);
-            set |= tbit(type);
+            set |= tbit(type) | (row_chunks(type, (int) in.k) % 64 != 0 ? SET_TAIL : 0u);
             const size_t colb = ((size_t) lds_col_bytes(fam, (int) in.k) + 15) & ~(size_t) 15;
             if (colb > lds_max) lds_max = colb;
             if ((size_t) in.k * 4 + 64 > stg_max) stg_max = (size_t) in.k * 4 + 64;
