@@ -54,7 +54,7 @@ __device__ __forceinline__ int dot16(const uint32_t w[4], const uint4 a) {
 // ------------------------------------------------------------------------------------------------
 struct Chunk {
     uint4    q;        // payload
-    uint4    a;        // Q4_K/Q5_K: header (d, dmin, 12 scale bytes)   Q6_K: qh bytes
+    uint4    a;        // Q4_K/Q5_K: header (d, dmin, 12 scale bytes as 4 records)   Q6_K: qh bytes
     uint4    b;        // Q5_K: qh bytes
     uint32_t sc;       // Q6_K: the two int8 sub-block scales (bytes 0 and 1)
     uint32_t dh;       // f16 super-scale (Q6_K, Q8_0, Q4_0)
@@ -63,18 +63,18 @@ struct Chunk {
 template <int T> __device__ __forceinline__ void chunk_load(Chunk & ch, const uint8_t * row, int nb, int s, int lane);
 template <int T, int NCOLS> struct Consume;
 
-// K-quant 6-bit scale/min pairs of sub-blocks (2g, 2g+1) from the 12-byte field (w0,w1,w2), g lane-invariant.
-//   j <  4: sc = q[j] & 63,                     m = q[j+4] & 63
-//   j >= 4: sc = (q[j+4] & 15) | (q[j-4]>>6)<<4, m = (q[j+4] >> 4) | (q[j]>>6)<<4      (ggml-quants.c:631-638)
+// K-quant 6-bit scale/min pairs of sub-blocks (2g, 2g+1) from the planar scale field (w0,w1,w2), g lane-invariant: record g of the
+// pack-time order (mi355q_common.h, k4_field_to_records) is one v_perm_b32 of a dword pair chosen by two hoisted selects, then four fields.
 __device__ __forceinline__ void k4_pairs(uint32_t w0, uint32_t w1, uint32_t w2, int g, int & sc0, int & sc1, int & mn0, int & mn1) {
-    const int sh = 16 * (g & 1);                                 // the pair sits in bytes (2g&3, 2g&3+1) of its dword
-    const uint32_t x0 = (w0 >> sh) & 0xFFFFu, x1 = (w1 >> sh) & 0xFFFFu, x2 = (w2 >> sh) & 0xFFFFu;
-    const uint32_t sc_lo = x0 & 0x3F3Fu, mn_lo = x1 & 0x3F3Fu;
-    const uint32_t sc_hi = (x2 & 0x0F0Fu) | (((x0 >> 6) & 0x0303u) << 4);
-    const uint32_t mn_hi = ((x2 >> 4) & 0x0F0Fu) | (((x1 >> 6) & 0x0303u) << 4);
-    const uint32_t sc = g < 2 ? sc_lo : sc_hi, mn = g < 2 ? mn_lo : mn_hi;
-    sc0 = (int) (sc & 0xFFu); sc1 = (int) (sc >> 8); mn0 = (int) (mn & 0xFFu); mn1 = (int) (mn >> 8);
+    const uint32_t r = k4_record(w0, w1, w2, g);
+    sc0 = (int) (r & 63u); sc1 = (int) ((r >> 6) & 63u); mn0 = (int) ((r >> 12) & 63u); mn1 = (int) (r >> 18);
 }
+
+// Integer scale products of the Q4_K / Q5_K consumer on the full-rate 24-bit multiplier (v_mul_i32_i24 / v_mad_i32_i24) instead of
+// v_mul_lo_u32 / v_mad_u64_u32.  Exact: every factor fits in 24 signed bits and every product and sum in 31 -- a 6-bit scale or min times
+// a 16-element sum of (q <= 31) * (|y| <= 128) or a bsum (|.| <= 2048).  (The Q6_K consumer keeps plain products: its sums are differences
+// the compiler cannot bound, and the sign-extension it then inserts costs more than the multiplier saves.)
+__device__ __forceinline__ int imul24(int a, int b) { return __mul24(a, b); }
 
 // ---- Q4_K planar: [qs 128*nb][hdr(d,dmin,scales) 16*nb]                          ggml-common.h:285-296
 template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_Q4_K>(Chunk & ch, const uint8_t * row, int nb, int s, int lane) {
@@ -93,9 +93,9 @@ template <int NCOLS> __device__ __forceinline__ void consume_q4k_q5k(const uint3
 #pragma unroll
     for (int n = 0; n < NCOLS; ++n) {
         const int s0 = dot16(lo, av[n].q16(e)), s1 = dot16(hi, av[n].q16(e + 32));
-        const int m  = mn0 * av[n].bsum(bi) + mn1 * av[n].bsum(bi + 2);
+        const int m  = imul24(mn0, av[n].bsum(bi)) + imul24(mn1, av[n].bsum(bi + 2));
         const float yd = av[n].dK(b);
-        acc[n] += (d * yd) * (float) (sc0 * s0 + sc1 * s1) - (dmin * yd) * (float) m;
+        acc[n] += (d * yd) * (float) (imul24(sc0, s0) + imul24(sc1, s1)) - (dmin * yd) * (float) m;
     }
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q4_K, NCOLS> {

@@ -15,6 +15,7 @@ struct PackDesc {
     int64_t row_bytes;
     int     perm_plane;    // plane whose bytes are additionally permuted inside each block (-1: none)
     uint8_t perm[16];      // device byte i of that plane's per-block group = source byte perm[i]
+    int     kq_plane;      // Q4_K / Q5_K header plane (-1: none): bytes 4..15 are the scale field as records (k4_field_to_records)
 };
 
 // one thread per 16-bit word of the device row image; PACK: canonical -> device, else device -> canonical
@@ -33,6 +34,17 @@ k_repack(const uint16_t * __restrict__ src, uint16_t * __restrict__ dst, const P
         const int64_t blk = rel / d.bytes[p];
         const int64_t off = rel - blk * d.bytes[p];
         const int64_t rbase = row * words_per_row;
+        if (p == d.kq_plane && off >= 4) {                           // the 12-byte scale field is one unit: its first word's thread does it all
+            if (off != 4) continue;
+            const int64_t c = blk * d.bsize + d.src_off[p] + 4;      // (even: the field's words are words of both rows)
+            uint8_t in[12], out[12];
+            const uint16_t * s16 = src + rbase + (PACK ? c : o) / 2;
+            for (int i = 0; i < 6; ++i) { in[2 * i] = (uint8_t) (s16[i] & 0xFF); in[2 * i + 1] = (uint8_t) (s16[i] >> 8); }
+            if (PACK) k4_field_to_records(in, out); else k4_records_to_field(in, out);
+            uint16_t * d16 = dst + rbase + (PACK ? o : c) / 2;
+            for (int i = 0; i < 6; ++i) d16[i] = (uint16_t) (out[2 * i] | (out[2 * i + 1] << 8));
+            continue;
+        }
         if (p == d.perm_plane) {                                     // two bytes of this word come from different places
             const int64_t c0 = blk * d.bsize + d.src_off[p] + d.perm[off], c1 = blk * d.bsize + d.src_off[p] + d.perm[off + 1];
             if (PACK) {
@@ -65,6 +77,7 @@ static bool make_desc(int type, int64_t k, PackDesc & d) {
     d.start[4] = off;
     d.perm_plane = -1;
     for (int i = 0; i < 16; ++i) d.perm[i] = (uint8_t) i;
+    d.kq_plane = type == MI355Q_TYPE_Q4_K ? 1 : (type == MI355Q_TYPE_Q5_K ? 2 : -1);   // (d, dmin, scales): the plane whose src_off is 0
     if (type == MI355Q_TYPE_Q6_K) {
         // gemv_fast.hip: chunk j = 4h + 2cc + p reads its two int8 scales (sub-blocks 8h+2cc+p and +4) as ONE 16-bit load
         d.perm_plane = 2;

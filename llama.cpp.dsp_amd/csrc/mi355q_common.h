@@ -191,21 +191,49 @@ __device__ __forceinline__ float expf_libm(float x, unsigned long long tab) {   
 // (2^-13 of the operations: one or two elements of an attention output).  The empty asm pins the f32 value in a register between the two roundings.
 __device__ __forceinline__ float f16_round(float x) { asm volatile("" : "+v"(x)); return __half2float(__float2half_rn(x)); }
 
-// K-quant 6-bit (scale, min) pair j out of the 12-byte field given as three dwords
-// (get_scale_min_k4, ggml/src/ggml-quants.c:631-638)
-__device__ __forceinline__ uint32_t byte_of3(uint32_t w0, uint32_t w1, uint32_t w2, int idx) {
-    const uint32_t w = idx < 4 ? w0 : (idx < 8 ? w1 : w2);
-    return (w >> (8 * (idx & 3))) & 0xFFu;
-}
-__device__ __forceinline__ void k4_scale_min(uint32_t w0, uint32_t w1, uint32_t w2, int j, int & sc, int & mn) {
-    if (j < 4) {
-        sc = (int) (byte_of3(w0, w1, w2, j) & 63u);
-        mn = (int) (byte_of3(w0, w1, w2, j + 4) & 63u);
-    } else {
-        const uint32_t a = byte_of3(w0, w1, w2, j + 4);
-        sc = (int) ((a & 0x0Fu) | ((byte_of3(w0, w1, w2, j - 4) >> 6) << 4));
-        mn = (int) ((a >> 4)    | ((byte_of3(w0, w1, w2, j)     >> 6) << 4));
+// Planar Q4_K / Q5_K header: the 12 scale bytes are stored as four 24-bit RECORDS, record g (sub-blocks 2g, 2g+1) at bytes 3g..3g+2 of the field:
+//   r_g = sc(2g) | sc(2g+1) << 6 | mn(2g) << 12 | mn(2g+1) << 18
+// with sc / mn the 6-bit values of get_scale_min_k4 (ggml/src/ggml-quants.c:631-638).  The 96 bits are the canonical 96 bits rearranged
+// (k_repack, layout.hip, at load time), so a lane reads its pair with one byte permute instead of re-deriving it from three bytes on every step.
+__host__ __device__ inline void k4_field_to_records(const uint8_t q[12], uint8_t r[12]) {
+    for (int g = 0; g < 4; ++g) {
+        uint32_t v = 0;
+        for (int t = 0; t < 2; ++t) {
+            const int j = 2 * g + t;
+            const int sc = j < 4 ? (q[j] & 63) : ((q[j + 4] & 0x0F) | ((q[j - 4] >> 6) << 4));
+            const int mn = j < 4 ? (q[j + 4] & 63) : ((q[j + 4] >> 4) | ((q[j] >> 6) << 4));
+            v |= (uint32_t) sc << (6 * t) | (uint32_t) mn << (12 + 6 * t);
+        }
+        r[3 * g] = (uint8_t) v; r[3 * g + 1] = (uint8_t) (v >> 8); r[3 * g + 2] = (uint8_t) (v >> 16);
     }
+}
+__host__ __device__ inline void k4_records_to_field(const uint8_t r[12], uint8_t q[12]) {
+    int sc[8], mn[8];
+    for (int g = 0; g < 4; ++g) {
+        const uint32_t v = r[3 * g] | (uint32_t) r[3 * g + 1] << 8 | (uint32_t) r[3 * g + 2] << 16;
+        sc[2 * g] = v & 63; sc[2 * g + 1] = (v >> 6) & 63; mn[2 * g] = (v >> 12) & 63; mn[2 * g + 1] = (v >> 18) & 63;
+    }
+    for (int j = 0; j < 4; ++j) {
+        q[j]     = (uint8_t) (sc[j] | (sc[j + 4] >> 4) << 6);
+        q[j + 4] = (uint8_t) (mn[j] | (mn[j + 4] >> 4) << 6);
+        q[j + 8] = (uint8_t) ((sc[j + 4] & 0x0F) | (mn[j + 4] & 0x0F) << 4);
+    }
+}
+
+// record g (low 24 bits, top byte 0) of the planar scale field given as three dwords: records 0, 1 lie in (w0, w1), records 2, 3 in (w1, w2).
+// With g lane-invariant the selector and both selects' conditions are hoisted: two v_cndmask_b32 and one v_perm_b32 per use.
+__device__ __forceinline__ uint32_t k4_record_sel(int g) {
+    const uint32_t o = g < 2 ? 3 * g : 3 * g - 4;                  // first byte of the record inside its dword pair
+    return o | (o + 1) << 8 | (o + 2) << 16 | 0x0Cu << 24;         // (selector 0x0C: a zero byte)
+}
+__device__ __forceinline__ uint32_t k4_record(uint32_t w0, uint32_t w1, uint32_t w2, int g) {
+    return __builtin_amdgcn_perm(g < 2 ? w1 : w2, g < 2 ? w0 : w1, k4_record_sel(g));
+}
+// K-quant 6-bit (scale, min) pair j out of the planar scale field
+__device__ __forceinline__ void k4_scale_min(uint32_t w0, uint32_t w1, uint32_t w2, int j, int & sc, int & mn) {
+    const uint32_t r = k4_record(w0, w1, w2, j >> 1) >> (6 * (j & 1));
+    sc = (int) (r & 63u);
+    mn = (int) ((r >> 12) & 63u);
 }
 
 #endif // __HIPCC__

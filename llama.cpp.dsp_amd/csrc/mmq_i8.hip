@@ -172,11 +172,10 @@ k_mmq_i8_q4k(const I8Mats mats, const uint8_t * __restrict__ xq, const uint8_t *
         for (int rt = 0; rt < RT; ++rt) {
             const uint4 hd = rh[rt];
             dW[rt] = h2f(hd.x & 0xFFFFu); dmW[rt] = h2f(hd.x >> 16);
-            // this lane's groups: 2h, 2h+1 (scale bytes 2h, 2h+1 / min bytes 4+2h, 5+2h) and 4+2h, 5+2h (bytes 8+2h, 9+2h + the top bits)   [get_scale_min_k4]
-            const uint32_t a = (hd.y >> h16) & 0xFFFFu, bb = (hd.z >> h16) & 0xFFFFu, c = (hd.w >> h16) & 0xFFFFu;
-            const int sc0 = a & 63, sc1 = (a >> 8) & 63, mn0 = bb & 63, mn1 = (bb >> 8) & 63;
-            const int sc2 = (c & 0xF) | (((a >> 6) & 3) << 4), sc3 = ((c >> 8) & 0xF) | (((a >> 14) & 3) << 4);
-            const int mn2 = ((c >> 4) & 0xF) | (((bb >> 6) & 3) << 4), mn3 = ((c >> 12) & 0xF) | (((bb >> 14) & 3) << 4);
+            // this lane's groups: 2h, 2h+1 (record h of the planar scale field) and 4+2h, 5+2h (record h+2)   [k4_field_to_records]
+            const uint32_t ra = k4_record(hd.y, hd.z, hd.w, h16 >> 4), rb = k4_record(hd.y, hd.z, hd.w, (h16 >> 4) + 2);
+            const int sc0 = ra & 63, sc1 = (ra >> 6) & 63, mn0 = (ra >> 12) & 63, mn1 = ra >> 18;
+            const int sc2 = rb & 63, sc3 = (rb >> 6) & 63, mn2 = (rb >> 12) & 63, mn3 = rb >> 18;
             const int scs[4] = { sc0, sc1, sc2, sc3 };
             const uint32_t raw[2][4] = { { rq0[rt].x, rq0[rt].y, rq0[rt].z, rq0[rt].w }, { rq1[rt].x, rq1[rt].y, rq1[rt].z, rq1[rt].w } };
 #pragma unroll
