@@ -213,15 +213,23 @@ int    mi355q_mul_mat_id(int type, const void *w, int64_t w_stride_bytes, int64_
  * run(): asynchronous on `stream`.  status(): synchronizes; 1 = a poll timed out (plan unusable).                         */
 #define MI355Q_STAGE_DEPENDS  0x1    /* (API version 1; accepted and ignored: dependencies follow from the operand addresses) */
 #define MI355Q_STAGE_NO_PLAIN 0x2    /* do not store plain f32 copies of this stage's outputs                               */
-/* ATTN stages over a QUANTIZED KV cache (-ctk q8_0 -ctv q8_0 / q4_0): both the K and the V cache hold blocks of that type (no bit: f16).
- * Block b (32 elements) of kv head g's row at position j is at  cache + j*nb_pos + g*nb_head + b*BB,  BB = 34 (q8_0) or 18 (q4_0); addresses
- * and strides must be even.  Only the flash layout (V rows per position, v_nb_dim = BB) is taken, with head_dim % 32 == 0.  This token's K and
- * V rows are quantized as mi355q_op_cpy (f32 -> q8_0 / q4_0) quantizes them and stored as contiguous rows at *k_dst / *v_dst (v_dst_nb is
- * ignored); the scores and P.V read them back as blocks, as the CPU does.  One split per head: the output is mi355q_op_flash_attn_ext's on the
- * same cache, bit for bit; several (windows above 256 positions) merge per-split F32 accumulators.  plan_create refuses a
- * window whose per-split K / V blocks do not fit the LDS (the message gives the limit) and the ring engine (MI355Q_PLAN_ENGINE=ring).      */
+/* ATTN stages over a QUANTIZED KV cache (-ctk T -ctv T, T = q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl): both the K and the V cache hold blocks of
+ * that type (no bit: f16; at most one bit).  Block b (32 elements) of kv head g's row at position j is at  cache + j*nb_pos + g*nb_head + b*BB,
+ * BB = 34 (q8_0), 18 (q4_0), 20 (q4_1), 22 (q5_0), 24 (q5_1), 18 (iq4_nl); addresses and strides must be even.  Only the flash layout (V rows per
+ * position, v_nb_dim = BB) is taken, with head_dim % 32 == 0.  This token's K and V rows are quantized as mi355q_op_cpy (f32 -> T) quantizes
+ * them and stored as contiguous rows at *k_dst / *v_dst (v_dst_nb is ignored); the scores and P.V read them back as blocks, as the CPU does.
+ * One split per head: the output is mi355q_op_flash_attn_ext's on the same cache, bit for bit; several (windows above 256 positions) merge
+ * per-split F32 accumulators.  plan_create refuses a window whose per-split K / V blocks do not fit the LDS (the message
+ * gives the type's limit) and the ring engine (MI355Q_PLAN_ENGINE=ring).
+ * The q4_1 / q5_0 / q5_1 / iq4_nl bits were added without a change of MI355Q_API_VERSION (no function or structure changed): a library older
+ * than them does not know the bits and reads such a stage as an f16 cache.  A caller that may meet an older library checks first that
+ * mi355q_op_flash_attn_ext accepts k / v of the type (MI355Q_ERR_UNSUPPORTED otherwise), as it does for the ops it dispatches.               */
 #define MI355Q_STAGE_KV_Q8_0  0x4
 #define MI355Q_STAGE_KV_Q4_0  0x8
+#define MI355Q_STAGE_KV_Q4_1   0x10
+#define MI355Q_STAGE_KV_Q5_0   0x20
+#define MI355Q_STAGE_KV_Q5_1   0x40
+#define MI355Q_STAGE_KV_IQ4_NL 0x80
 #define MI355Q_STAGE_GEMV 0
 #define MI355Q_STAGE_ATTN 1
 #define MI355Q_X_PLAIN     0
@@ -319,6 +327,9 @@ int     mi355q_plan_destroy(mi355q_plan *plan);
  *                                           frequency factors (src2); pos = i32 device [ne2]
  *   op_mul_mat_f  GGML_OP_MUL_MAT           with an f16, bf16 or f32 src0 (attention KQ / KQV): dst[m,n] = sum_k a[k,m] b[k,n],
  *                                           dims 2/3 of src0 broadcast; an f16 / bf16 src0 rounds src1 to f16 / bf16 as the CPU does
+ *                                           src0 may also be a view of a quantized KV cache (MI355Q_TYPE_Q8_0 / _Q4_0 / _Q4_1 / _Q5_0 / _Q5_1 /
+ *                                           _IQ4_NL, nb[0] = block bytes, rows of <= 256 elements in whole blocks): src1 rows are
+ *                                           quantized to the type's vec_dot_type and each output is the type's vec_dot, as on the CPU
  *   op_get_rows   GGML_OP_GET_ROWS          f32 / f16 / bf16 rows -> f32                                                          */
 #define MI355Q_T_F32 0
 #define MI355Q_T_F16 1
@@ -355,6 +366,10 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
  *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256, n_kv <= 36864.
  * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
  * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types are not accepted.
+ * k / v may also both hold blocks of one quantized cache type (MI355Q_TYPE_Q8_0, _Q4_0, _Q4_1, _Q5_0, _Q5_1, _IQ4_NL; nb[0] = the block's bytes,
+ * head sizes of whole 32-blocks, n_kv <= 8192): the CPU's arithmetic for that type; with >= 16 query rows and the
+ * workspace the cache is decoded once into f16 scratch for the matrix-core path.  mi355q_op_cpy / _indirect store f32 into such a cache
+ * (contiguous destination, source rows of whole 32-blocks) with the bytes of the CPU's from_float of the type.
  * workspace (optional, mi355q_op_flash_attn_ext_workspace bytes): with it, a call with few query rows (decode) splits the KV range over
  * several workgroups per row and merges the pieces in a second launch, and a call with >= 16 query rows (prefill) computes scores,
  * softmax and P V on the matrix-core kernels with the scores of the batch in the workspace; without it every row is one workgroup.   */

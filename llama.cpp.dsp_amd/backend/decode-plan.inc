@@ -124,9 +124,9 @@ struct mi355_plan_matcher {
             memcpy(&scale, (const float *) sm->op_params + 0, 4); memcpy(&max_bias, (const float *) sm->op_params + 1, 4);
         }
         if (max_bias != 0.0f || softcap != 0.0f) return false;
-        // the cache: f16, or (flash graphs only) both K and V in Q8_0 or both in Q4_0 blocks (-ctk q8_0 -ctv q8_0): the stage flag MI355Q_STAGE_KV_*
+        // the cache: f16, or (flash graphs only) both K and V in blocks of one of Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL (-ctk T -ctv T): the stage flag MI355Q_STAGE_KV_*
         const enum ggml_type kvt = kview->type;
-        const bool kv_quant = fa && (kvt == GGML_TYPE_Q8_0 || kvt == GGML_TYPE_Q4_0);
+        const bool kv_quant = fa && mi355_kv_block_type(kvt);
         const size_t kv_nb0 = kv_quant ? ggml_type_size(kvt) : 2;                              // bytes per element (f16) or per 32-block
         if ((kvt != GGML_TYPE_F16 && !kv_quant) || vview->type != kvt || !kview->view_src || !vview->view_src || kview->nb[0] != kv_nb0) return false;
         const struct ggml_tensor * rq = mi355_skip_views(qperm);
@@ -146,7 +146,7 @@ struct mi355_plan_matcher {
             else if (n->src[1]->view_src == vview->view_src) { if (cv) return false; cv = n; }
         }
         if (!ck || !cv || ck->src[1]->type != kvt || cv->src[1]->type != kvt) return false;
-        if (kv_quant && (ck->src[0]->type != GGML_TYPE_F32 || cv->src[0]->type != GGML_TYPE_F32)) return false;       // CPY f32 -> q8_0 / q4_0
+        if (kv_quant && (ck->src[0]->type != GGML_TYPE_F32 || cv->src[0]->type != GGML_TYPE_F32)) return false;       // CPY f32 -> the cache type
         const struct ggml_tensor * rk = mi355_skip_views(ck->src[0]);
         if (!rk || rk->op != GGML_OP_ROPE || rk->src[1] != rq->src[1] || rk->src[2] != rq->src[2]) return false;
         if (memcmp(rk->op_params, rq->op_params, sizeof(rk->op_params)) != 0) return false;
@@ -203,7 +203,8 @@ struct mi355_plan_matcher {
                     cpy_ordinal[(size_t) idx(ck)], cpy_ordinal[(size_t) idx(cv)], ck->data, cv->data, (long long) a->v_dst_nb, a->mask, a->mask_f16, a->scale, (void *) a->out);
         mi355q_stage st; memset(&st, 0, sizeof(st));
         st.kind = MI355Q_STAGE_ATTN; st.attn = a; st.flags = MI355Q_STAGE_NO_PLAIN;
-        if (kv_quant) st.flags |= kvt == GGML_TYPE_Q8_0 ? MI355Q_STAGE_KV_Q8_0 : MI355Q_STAGE_KV_Q4_0;
+        if (kv_quant) st.flags |= kvt == GGML_TYPE_Q8_0 ? MI355Q_STAGE_KV_Q8_0 : kvt == GGML_TYPE_Q4_0 ? MI355Q_STAGE_KV_Q4_0 : kvt == GGML_TYPE_Q4_1 ? MI355Q_STAGE_KV_Q4_1 :
+                                  kvt == GGML_TYPE_Q5_0 ? MI355Q_STAGE_KV_Q5_0 : kvt == GGML_TYPE_Q5_1 ? MI355Q_STAGE_KV_Q5_1 : MI355Q_STAGE_KV_IQ4_NL;
         b.stages.push_back(st);
         b.anchor.push_back(idx(fa ? fa : kq));
         b.outs.push_back({ top });

@@ -10,9 +10,9 @@
 // device, the f32 / f16 ops between those matmuls.  supports_op is true for
 //   * GGML_OP_MUL_MAT    with quantized src0 (the 19 types of mi355q_type_supported) or f16 / bf16 / f32 src0, f32 src1, f32 dst
 //   * GGML_OP_MUL_MAT_ID with the same quantized src0 types (expert ids stay on the device)
-//   * ADD SUB MUL DIV SCALE, UNARY (SILU RELU SIGMOID TANH NEG ABS), RMS_NORM, CPY CONT DUP (among f32 / f16 / bf16; f32 -> q8_0 / q4_0),
-//     GET_ROWS (f32 / f16 / bf16 rows), SOFT_MAX, ROPE, FLASH_ATTN_EXT (f16, bf16, q8_0 or q4_0 K / V), ARGSORT, SUM_ROWS -- the variants
-//     a llama / mixtral graph uses (mi355_supports_op lists them); so -ctk / -ctv f16, bf16, q8_0 and q4_0 caches stay resident
+//   * ADD SUB MUL DIV SCALE, UNARY (SILU RELU SIGMOID TANH NEG ABS), RMS_NORM, CPY CONT DUP (among f32 / f16 / bf16; f32 -> q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl),
+//     GET_ROWS (f32 / f16 / bf16 rows), SOFT_MAX, ROPE, FLASH_ATTN_EXT (f16, bf16 or one quantized cache type for K / V), ARGSORT, SUM_ROWS -- the variants
+//     a llama / mixtral graph uses (mi355_supports_op lists them); so all nine -ctk / -ctv cache types (f32, f16, bf16, q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl) stay resident
 //   * the no-op view ops NONE / RESHAPE / VIEW / PERMUTE / TRANSPOSE on our own buffers
 // everything else stays on the CPU backend.  The fork's own DSP backend (ggml/src/ggml-dsp/ggml-dsp.cpp)
 // is the structural template for where each hook goes; none of its code is reused.
@@ -115,11 +115,22 @@ static bool mi355_is_quant(enum ggml_type t) { return mi355q_type_supported((int
 // the tensor whose shape defines the device row layout (views share their source's rows)
 static const struct ggml_tensor * mi355_root(const struct ggml_tensor * t) { return t->view_src ? t->view_src : t; }
 
-// A Q8_0 / Q4_0 tensor outside a weight buffer is (or may become) a KV cache (-ctk q8_0 / q4_0, -ctv ...): the device writes its rows block by block (CPY) and the
-// attention kernel reads heads out of them, so it keeps the CANONICAL block order; only Q8_0 tensors in buffers the application marked as weights are planar.
+// A tensor of a KV-cache block type (-ctk / -ctv q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl) outside a weight buffer is (or may become) a KV cache: the device writes
+// its rows block by block (CPY) and the attention kernel reads heads out of them, so it keeps the CANONICAL block order; of these types only Q8_0 / Q4_0 / IQ4_NL
+// have a planar weight layout at all, and only tensors in buffers the application marked as weights take it.
+static bool mi355_kv_block_type(enum ggml_type t) {
+    return t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL;
+}
 static bool mi355_q80_canonical(const struct ggml_tensor * t) {
     const struct ggml_tensor * r = mi355_root(t);
-    return (t->type == GGML_TYPE_Q8_0 || t->type == GGML_TYPE_Q4_0) && !(r->buffer && r->buffer->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS);
+    return mi355_kv_block_type(t->type) && !(r->buffer && r->buffer->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS);
+}
+// src0 of the KQ product of a -fa 0 graph over a quantized K cache: a view with rows of head_dim elements cut out of the cache's long canonical rows
+// (llama-graph.cpp: ggml_view_3d of the 1-D cache tensor).  It goes to the cache-view form of mi355q_op_mul_mat_f (the CPU's vec_dot per position), not
+// to the weight kernels, whose device rows are whole rows of the root tensor.
+static bool mi355_kv_view_mat(const struct ggml_tensor * a) {
+    return mi355_q80_canonical(a) && a->view_src && mi355_root(a)->ne[0] != a->ne[0] && a->nb[0] == ggml_type_size(a->type) &&
+           a->ne[0] % 32 == 0 && a->ne[0] <= 256 && a->nb[1] % 2 == 0 && a->nb[2] % 2 == 0 && a->nb[3] % 2 == 0;
 }
 // rows of a quantized tensor are stored planar iff (type, ne0, and for Q8_0 the buffer's usage) say so -- same predicate everywhere
 static bool mi355_rows_planar(const struct ggml_tensor * t) {
@@ -380,8 +391,12 @@ static mi355q_tensor mi355_td(const struct ggml_tensor * t) {
     case GGML_TYPE_I32:  d.type = MI355Q_T_F32;     break;     // (row ids of GET_ROWS: 4-byte elements, read as int32 by the op)
     case GGML_TYPE_F16:  d.type = MI355Q_T_F16;     break;
     case GGML_TYPE_BF16: d.type = MI355Q_T_BF16;    break;     // (a bf16 KV cache, a bf16 embedding table)
-    case GGML_TYPE_Q8_0: d.type = MI355Q_TYPE_Q8_0; break;     // (Q8_0 / Q4_0: a quantized KV cache, CPY destination / FLASH_ATTN_EXT operand)
+    case GGML_TYPE_Q8_0: d.type = MI355Q_TYPE_Q8_0; break;     // (the block types of a quantized KV cache, CPY destination / FLASH_ATTN_EXT operand)
     case GGML_TYPE_Q4_0: d.type = MI355Q_TYPE_Q4_0; break;
+    case GGML_TYPE_Q4_1: d.type = MI355Q_TYPE_Q4_1; break;
+    case GGML_TYPE_Q5_0: d.type = MI355Q_TYPE_Q5_0; break;
+    case GGML_TYPE_Q5_1: d.type = MI355Q_TYPE_Q5_1; break;
+    case GGML_TYPE_IQ4_NL: d.type = MI355Q_TYPE_IQ4_NL; break;
     default: GGML_ABORT("mi355_td: tensor type %s has no residency-op form", ggml_type_name(t->type));
     }
     for (int i = 0; i < 4; ++i) { d.ne[i] = t->ne[i]; d.nb[i] = (int64_t) t->nb[i]; }
@@ -463,7 +478,7 @@ static void mi355_glue_op(mi355_backend_ctx * ctx, struct ggml_tensor * dst, int
         memcpy(&p.attn_factor, q + 8, 4); memcpy(&p.beta_fast, q + 9, 4); memcpy(&p.beta_slow, q + 10, 4);
         MQ_CHECK(mi355q_op_rope(&a, (const int32_t *) dst->src[1]->data, dst->src[2] ? (const float *) dst->src[2]->data : nullptr, &d, &p, ctx->stream));
     } break;
-    case GGML_OP_MUL_MAT: {                                   // f16 / bf16 / f32 src0 (the quantized types go through mi355_mul_mat)
+    case GGML_OP_MUL_MAT: {                                   // f16 / bf16 / f32 src0 or a quantized KV-cache view (quantized weights go through mi355_mul_mat)
         const mi355q_tensor b = mi355_td(dst->src[1]);
         MQ_CHECK(mi355q_op_mul_mat_f(&a, &b, &d, ctx->stream));
     } break;
@@ -613,7 +628,7 @@ static enum ggml_status mi355_issue_nodes(mi355_backend_ctx * ctx, struct ggml_c
         case GGML_OP_NONE: case GGML_OP_RESHAPE: case GGML_OP_VIEW: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE:
             break;
         case GGML_OP_MUL_MAT:
-            if (!mi355_is_quant(node->src[0]->type)) { mi355_glue_op(ctx, node); break; }
+            if (!mi355_is_quant(node->src[0]->type) || mi355_kv_view_mat(node->src[0])) { mi355_glue_op(ctx, node); break; }
             if (fz && mi355_joinable_mat(node)) {                 // other matmuls on the same activations (at most 4 per launch)
                 int idx[4] = { i, -1, -1, -1 }, n = 1;
                 for (int j = i + 1; j < cgraph->n_nodes && j <= i + 24 && n < 4; ++j) {
@@ -997,6 +1012,8 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         }
         if (!mi355_is_quant(a->type) || b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32) return false;
         if (!mi355_operand_ok(a)) return false;
+        if (mi355_kv_view_mat(a))                                 // a quantized K cache read by a plain MUL_MAT (-fa 0 -ctk q8_0 / ... / iq4_nl)
+            return b->nb[0] == sizeof(float) && op->nb[0] == sizeof(float) && b->ne[1] <= 0x7FFFFFFF && b->ne[2] <= 65535 && b->ne[3] <= 65535 && mi355_operand_ok(b);
         // src0: whole rows of its root tensor, rows dense, 16-byte aligned row pitch where the rows are planar
         if (a->nb[0] != ggml_type_size(a->type) || mi355_root(a)->ne[0] != a->ne[0]) return false;
         if (a->nb[1] < ggml_row_size(a->type, a->ne[0])) return false;
@@ -1037,7 +1054,7 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
     }
     case GGML_OP_CPY: case GGML_OP_CONT: case GGML_OP_DUP: {
         const struct ggml_tensor * a = op->src[0];
-        if (op->op == GGML_OP_CPY && (op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q4_0))      // the K / V stores of a quantized cache (-ctk q8_0 / q4_0): whole blocks, contiguous destination
+        if (op->op == GGML_OP_CPY && mi355_kv_block_type(op->type))      // the K / V stores of a quantized cache (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl): whole blocks, contiguous destination
             return a->type == GGML_TYPE_F32 && mi355_operand_ok(a) && a->nb[0] == sizeof(float) && a->ne[0] % 32 == 0 && op->ne[0] % 32 == 0 &&
                    ggml_is_contiguous(op) && ggml_nelements(a) == ggml_nelements(op) && mi355_q80_canonical(op);
         return mi355_float_type(a->type) && mi355_float_type(op->type) && mi355_operand_ok(a) && ggml_nelements(a) == ggml_nelements(op);
@@ -1067,11 +1084,11 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         if (op->src[2] && op->src[2]->type != GGML_TYPE_F32) return false;
         return a->ne[0] % 2 == 0;
     }
-    case GGML_OP_FLASH_ATTN_EXT: {                            // f16, bf16, Q8_0 or Q4_0 KV cache, f32 queries, f16 mask; other cache types stay on the CPU
+    case GGML_OP_FLASH_ATTN_EXT: {                            // f16, bf16 or quantized (K and V of one block type) KV cache, f32 queries, f16 mask; mixed K / V types stay on the CPU
         const struct ggml_tensor * q = op->src[0], * k = op->src[1], * v = op->src[2], * m = op->src[3];
-        const bool kv_q80 = (k->type == GGML_TYPE_Q8_0 && v->type == GGML_TYPE_Q8_0) || (k->type == GGML_TYPE_Q4_0 && v->type == GGML_TYPE_Q4_0);       // a Q8_0 / Q4_0 cache: the one-workgroup-per-row kernel with the CPU's arithmetic
+        const bool kv_q80 = k->type == v->type && mi355_kv_block_type(k->type);       // a quantized cache: the one-workgroup-per-row kernel with the CPU's arithmetic
         const bool kv_bf16 = k->type == GGML_TYPE_BF16 && v->type == GGML_TYPE_BF16;          // a bf16 cache: the same kernel's bf16 form, or the matrix cores for a batch
-        const size_t kv_bb = k->type == GGML_TYPE_Q4_0 ? 18u : 34u;
+        const size_t kv_bb = ggml_type_size(k->type);                                          // (bytes per 32-element block)
         if (q->type != GGML_TYPE_F32 || !((k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16) || kv_q80 || kv_bf16) || op->type != GGML_TYPE_F32) return false;
         if (kv_bf16 && k->ne[1] > 8192) return false;
         if (!mi355_operand_ok(q) || !mi355_operand_ok(k) || !mi355_operand_ok(v) || (m && !mi355_operand_ok(m))) return false;

@@ -202,16 +202,7 @@ template <int NCOLS> struct Consume<MI355Q_TYPE_Q4_0, NCOLS> {
 };
 
 // ---- the non-linear 4-bit formats: a nibble indexes the 16-entry code book kvalues_iq4nl (ggml-common.h; decoded by
-// dequantize_row_iq4_nl / _xs, ggml-quants.c:2434-2475).  Four nibbles held as bytes of a dword become four int8 with two v_perm_b32
-// (each picks among 8 table bytes by the low 3 bits) and one select on bit 3 -- no LDS table, no per-nibble loads.
-__device__ __forceinline__ uint32_t iq4_lut4(uint32_t nib) {
-    // the code book {-127,-104,-83,-65 | -49,-35,-22,-10 | 1,13,25,38 | 53,69,89,113} as little-endian dwords
-    const uint32_t sel = nib & 0x07070707u;
-    const uint32_t a = __builtin_amdgcn_perm(0xF6EADDCFu, 0xBFAD9881u, sel);      // entries 0..7
-    const uint32_t b = __builtin_amdgcn_perm(0x71594535u, 0x26190D01u, sel);      // entries 8..15
-    const uint32_t m = ((nib >> 3) & 0x01010101u) * 0xFFu;
-    return (a & ~m) | (b & m);
-}
+// dequantize_row_iq4_nl / _xs, ggml-quants.c:2434-2475) through iq4_lut4 (mi355q_common.h).
 
 // ---- IQ4_NL planar: [qs 16*nb][d 2*nb]; a chunk is one 32-block (low nibbles = elements 0..15, high = 16..31)      ggml-common.h block_iq4_nl
 template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_IQ4_NL>(Chunk & ch, const uint8_t * row, int nb, int s, int lane) {

@@ -101,6 +101,17 @@ __device__ __forceinline__ int dot4(int a, int b, int c) {
     return __builtin_amdgcn_sdot4(a, b, c, false);
 }
 
+// Four IQ4_NL / IQ4_XS nibbles held as bytes of a dword become four int8 code-book values (kvalues_iq4nl, ggml-common.h) with two v_perm_b32
+// (each picks among 8 table bytes by the low 3 bits) and one select on bit 3 -- no LDS table, no per-nibble loads.
+__device__ __forceinline__ uint32_t iq4_lut4(uint32_t nib) {
+    // the code book {-127,-104,-83,-65 | -49,-35,-22,-10 | 1,13,25,38 | 53,69,89,113} as little-endian dwords
+    const uint32_t sel = nib & 0x07070707u;
+    const uint32_t a = __builtin_amdgcn_perm(0xF6EADDCFu, 0xBFAD9881u, sel);      // entries 0..7
+    const uint32_t b = __builtin_amdgcn_perm(0x71594535u, 0x26190D01u, sel);      // entries 8..15
+    const uint32_t m = ((nib >> 3) & 0x01010101u) * 0xFFu;
+    return (a & ~m) | (b & m);
+}
+
 __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & 63); }
 
 // Loads of WEIGHT bytes name the global address space.  A pointer that arrives through a descriptor is generic to the compiler, and a generic

@@ -284,38 +284,25 @@ __global__ void __launch_bounds__(256) k_cpy_transpose(const TensorD a, TensorD 
 static int grid_for(int64_t n);
 static bool cpy_same_shape(const mi355q_tensor * a, const mi355q_tensor * d) { return a->ne[0] == d->ne[0] && a->ne[1] == d->ne[1] && a->ne[2] == d->ne[2] && a->ne[3] == d->ne[3]; }
 // picks the form; returns false when the generic element-wise kernel has to run
-// ---- CPY f32 -> Q8_0 (the K / V stores of a quantized cache, -ctk q8_0 / -ctv q8_0; the reference: ggml-cuda/cpy.cu:71,416-423, CPU: dup -> from_float) ----
+// ---- CPY f32 -> a KV-cache block type (the K / V stores of a quantized cache, -ctk / -ctv q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl; the reference:
+// ggml-cuda/cpy.cu:71,416-423, CPU: dup -> from_float) ----
 // The CPU quantizes source row by source row into a contiguous destination (ggml_compute_forward_dup_f32, quantized dst): logical block b of 32
-// elements -> bytes [34 b, 34 b + 34) of the destination.  Eight lanes own one block (q80_group8: quantize_row_q8_0_ref's arithmetic, round half
-// away from zero -- the CPU's SIMD quantizer rounds half to even, the same one-in-a-million tie as in the matmul path's activation quantizer).
-__global__ void __launch_bounds__(256) k_cpy_f32_q8_0(const TensorD a, char * dst, int64_t n_blocks, char * const * dest_table, int dest_index) {
+// elements -> bytes [BB b, BB b + BB) of the destination, with the type's quantize_row_<type>_ref (fa_quant.cuh kv_quant_group8).
+// Eight lanes own one block, lane l the elements 4l .. 4l+3; every lane of a wave takes part in the group reductions, so surplus groups redo the
+// last block.  Blocks are 2-byte aligned: they are stored as halves of a word.  (Q8_0: round half away from zero -- the CPU's SIMD quantizer rounds
+// half to even, the same one-in-a-million tie as in the matmul path's activation quantizer.)
+template <int KVT>
+__global__ void __launch_bounds__(256) k_cpy_f32_kvq(const TensorD a, char * dst, int64_t n_blocks, char * const * dest_table, int dest_index) {
     if (dest_table) dst = dest_table[dest_index];
     const int lane8 = threadIdx.x & 7;
-    for (int64_t b0 = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 3; b0 < ((n_blocks + 31) & ~(int64_t) 31); b0 += ((int64_t) gridDim.x * blockDim.x) >> 3) {
-        const int64_t b = b0 < n_blocks ? b0 : n_blocks - 1;    // (every lane of a wave takes part in the group reductions; surplus groups redo the last block)
-        const int64_t e = 32 * b + 4 * lane8;
-        const int64_t a0 = e % a.ne[0], ar = e / a.ne[0], a1 = ar % a.ne[1], ar2 = ar / a.ne[1], a2 = ar2 % a.ne[2], a3 = ar2 / a.ne[2];
-        const float * src = (const float *) (a.data + a0 * 4 + a1 * a.nb[1] + a2 * a.nb[2] + a3 * a.nb[3]);
-        const float4 v = make_float4(src[0], src[1], src[2], src[3]);
-        uint32_t q; float d;
-        kv_quant_group8<MI355Q_TYPE_Q8_0>(v, q, d);
-        if (b0 < n_blocks) kv_store_group8<MI355Q_TYPE_Q8_0>(dst + 34 * b, lane8, q, d);     // 2-byte aligned: the quants are stored as halves of a word
-    }
-}
-
-// CPY f32 -> Q4_0 (a Q4_0 cache): quantize_row_q4_0_ref (ggml-quants.c:31-66) -- max = the FIRST element of largest magnitude, signed; d = max / -8;
-// q = min(15, (int8) (x / d + 8.5)); byte j = q[j] | q[j + 16] << 4.  Eight lanes own a block (lane l: elements 4l .. 4l+3).
-__global__ void __launch_bounds__(256) k_cpy_f32_q4_0(const TensorD a, char * dst, int64_t n_blocks, char * const * dest_table, int dest_index) {
-    if (dest_table) dst = dest_table[dest_index];
-    const int lane = threadIdx.x & 63, lane8 = lane & 7;
     for (int64_t b0 = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 3; b0 < ((n_blocks + 31) & ~(int64_t) 31); b0 += ((int64_t) gridDim.x * blockDim.x) >> 3) {
         const int64_t b = b0 < n_blocks ? b0 : n_blocks - 1;
         const int64_t e = 32 * b + 4 * lane8;
         const int64_t a0 = e % a.ne[0], ar = e / a.ne[0], a1 = ar % a.ne[1], ar2 = ar / a.ne[1], a2 = ar2 % a.ne[2], a3 = ar2 / a.ne[2];
         const float * src = (const float *) (a.data + a0 * 4 + a1 * a.nb[1] + a2 * a.nb[2] + a3 * a.nb[3]);
-        uint32_t w; float d;
-        kv_quant_group8<MI355Q_TYPE_Q4_0>(make_float4(src[0], src[1], src[2], src[3]), w, d);
-        if (b0 < n_blocks) kv_store_group8<MI355Q_TYPE_Q4_0>(dst + 18 * b, lane8, w, d);
+        KvBlk o;
+        kv_quant_group8<KVT>(make_float4(src[0], src[1], src[2], src[3]), o);
+        if (b0 < n_blocks) kv_store_group8<KVT>(dst + kv_block_bytes<KVT>() * b, lane8, o);
     }
 }
 
@@ -729,24 +716,27 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
 // the maximum grows, v * weight by f32 fma per position (ggml_vec_scale_f32 / ggml_vec_mad_f32).
 // KVT = MI355Q_T_BF16 (a bf16 cache): q rounded to bf16 (ggml_compute_fp32_to_bf16), scores by ggml_vec_dot_bf16 in its AVX2 order (see
 // k_mul_mat_f; any head size: the tail past the last 32-chunk in double), V widened exactly to f32; the softmax walk and the F32 accumulator as above.
-template <int KVT>                                                          // MI355Q_TYPE_Q8_0 (34-byte blocks), MI355Q_TYPE_Q4_0 (18-byte blocks: f16 d, 16 bytes of nibbles, low = elements 0..15) or MI355Q_T_BF16
+// KVT = Q4_1 / Q5_0 / Q5_1 / IQ4_NL: the same walk with the type's own dot product and dequantization (fa_quant.cuh); q goes to Q8_1
+// (the block sums s after the packed quants) for Q4_1 / Q5_1.
+template <int KVT>                                                          // a block type of fa_quant.cuh (Q8_0: 34-byte blocks, Q4_0: 18, ...) or MI355Q_T_BF16
 __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD q, const TensorD k, const TensorD v, const TensorD m, int has_mask, const TensorD d,
                                                                    float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2) {
-    extern __shared__ __attribute__((aligned(16))) float fq_s[];             // [n_kv] scores -> weights | [n_kv] rescale factors | q: [DK / 32] block scales, [DK / 4] packed quants (bf16: [DK] rounded values)
-    constexpr int BB = KVT == MI355Q_TYPE_Q8_0 ? 34 : 18;                      // bytes per 32-element block of the cache (not used for bf16)
+    extern __shared__ __attribute__((aligned(16))) float fq_s[];             // [n_kv] scores -> weights | [n_kv] rescale factors | q: [DK / 32] block scales, [DK / 4] packed quants, [DK / 32] block sums (bf16: [DK] rounded values)
+    constexpr int BB = kv_block_bytes<KVT>();                                  // bytes per 32-element block of the cache (not used for bf16)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t t = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int64_t DK = k.ne[0], DV = v.ne[0], n_kv = k.ne[1];
     const int64_t hk = h / (q.ne[2] / k.ne[2]), hv = h / (q.ne[2] / v.ne[2]), bk = b / (q.ne[3] / k.ne[3]), bv = b / (q.ne[3] / v.ne[3]);
     float * msv = fq_s + n_kv, * qd = msv + n_kv;
     uint32_t * qq = (uint32_t *) (qd + (DK >> 5));
+    float * qsum = (float *) (qq + (DK >> 2));
     const float slope = max_bias > 0.0f ? ((uint32_t) h < n_head_log2 ? powf(m0, (float) (h + 1)) : powf(m1, (float) (2 * (h - n_head_log2) + 1))) : 1.0f;
     const __half * mp = has_mask ? (const __half *) (m.data + t * m.nb[1]) : nullptr;
     // ---- q -> Q8_0 (whole waves take part: the 8-lane reductions); q -> bf16
     if constexpr (KVT == MI355Q_T_BF16) {
         if (tid < DK) qd[tid] = bf16_round(((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]))[tid]);
     } else if (tid < ((DK / 4 + 63) & ~63)) {
-        fa_quantize_q((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]), tid, DK, qq, qd);     // (fa_quant.cuh)
+        fa_quantize_q<kv_has_min<KVT>()>((const float *) (q.data + t * q.nb[1] + h * q.nb[2] + b * q.nb[3]), tid, DK, qq, qd, qsum);     // (fa_quant.cuh)
     }
     __syncthreads();
     // ---- scores: one position per thread
@@ -778,7 +768,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
             if (softcap != 0.0f) s = softcap * tanhf(s);
             s = __fadd_rn(s, mv);
         } else if (mv != -INFINITY) {                                         // (a masked position is skipped by the CPU whatever its cache row holds)
-            if constexpr (KVT != MI355Q_T_BF16) s = fa_dot_q80<KVT>(k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3], qd, qq, nblk);     // (fa_quant.cuh)
+            if constexpr (KVT != MI355Q_T_BF16) s = fa_dot_q80<KVT>(k.data + j * k.nb[1] + hk * k.nb[2] + bk * k.nb[3], qd, qq, nblk, qsum);     // (fa_quant.cuh)
             s = __fmul_rn(s, scale);
             if (softcap != 0.0f) s = softcap * tanhf(s);
             s = __fadd_rn(s, mv);
@@ -811,20 +801,35 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext_q80(const TensorD
     }
 }
 
-// a quantized cache for the prefill path: K / V rows of all (kv head, batch) pairs -> F16 [B][H][n_kv][D] in scratch (value = q * d, rounded to f16), so that the
+// MUL_MAT with a quantized KV-cache view as src0 (the KQ product of a -fa 0 graph over -ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl: K rows of head_dim
+// elements, strided by position and head inside the cache's long rows, canonical blocks).  The CPU's arithmetic (ggml-cpu.c ggml_compute_forward_mul_mat):
+// the src1 row is quantized to the type's vec_dot_type by the SIMD quantizer and every output is the type's vec_dot -- fa_quantize_q / fa_dot_q80, the
+// scores of k_flash_attn_ext_q80 before the scale.  One workgroup per src1 row, a thread per src0 row (position).
+template <int KVT>
+__global__ void __launch_bounds__(256) k_mul_mat_kvq(const TensorD a, const TensorD b, const TensorD d) {
+    __shared__ float qd[8], qsum[8];
+    __shared__ uint32_t qq[64];
+    const int tid = threadIdx.x;
+    const int64_t n = blockIdx.x, i2 = blockIdx.y, i3 = blockIdx.z;
+    const int64_t K = a.ne[0], M = a.ne[1];
+    const int64_t a2 = i2 / (b.ne[2] / a.ne[2]), a3 = i3 / (b.ne[3] / a.ne[3]);
+    if (tid < 64) fa_quantize_q<kv_has_min<KVT>()>((const float *) (b.data + n * b.nb[1] + i2 * b.nb[2] + i3 * b.nb[3]), tid, K, qq, qd, qsum);     // (K <= 256: wave 0, whole)
+    __syncthreads();
+    const int nblk = (int) (K >> 5);
+    for (int64_t m = tid; m < M; m += 256)
+        *(float *) (d.data + m * d.nb[0] + n * d.nb[1] + i2 * d.nb[2] + i3 * d.nb[3]) = fa_dot_q80<KVT>(a.data + m * a.nb[1] + a2 * a.nb[2] + a3 * a.nb[3], qd, qq, nblk, qsum);
+}
+
+// a quantized cache for the prefill path: K / V rows of all (kv head, batch) pairs -> F16 [B][H][n_kv][D] in scratch (value = dequantize_row_<type>'s, rounded to f16), so that the
 // matrix-core kernels of the f16 path can take them.  One thread per element pair.
 template <int KVT>
 __global__ void __launch_bounds__(256) k_dequant_cache_f16(const TensorD t, __half * __restrict__ out) {
-    constexpr int BB = KVT == MI355Q_TYPE_Q8_0 ? 34 : 18;
+    constexpr int BB = kv_block_bytes<KVT>();
     const int64_t D = t.ne[0], n_kv = t.ne[1], H = t.ne[2], B = t.ne[3], n = D * n_kv * H * B;
     for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t) gridDim.x * blockDim.x) {
         const int64_t e = i % D, r = i / D, j = r % n_kv, r2 = r / n_kv, h = r2 % H, b = r2 / H;
         const char * blk = t.data + j * t.nb[1] + h * t.nb[2] + b * t.nb[3] + BB * (e >> 5);
-        const int ee = (int) (e & 31);
-        int qv;
-        if constexpr (KVT == MI355Q_TYPE_Q8_0) qv = (int) *(const int8_t *) (blk + 2 + ee);
-        else { const int byte = (int) *(const uint8_t *) (blk + 2 + (ee & 15)); qv = ((ee < 16 ? byte : byte >> 4) & 15) - 8; }
-        out[i] = __float2half_rn(__fmul_rn((float) qv, __half2float(*(const __half *) blk)));
+        out[i] = __float2half_rn(kv_dequant_elem<KVT>(blk, (int) (e & 31)));
     }
 }
 
@@ -1107,15 +1112,24 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor * a, const mi355q_tensor * 
     OPS_LAUNCHED();
 }
 
-// f32 -> Q8_0: contiguous destination, source rows of whole blocks with unit stride along dim 0 (what ggml_compute_forward_dup_f32 requires too)
-static int cpy_to_q8_0(const mi355q_tensor * a, const mi355q_tensor * dst, char * const * table, int index, hipStream_t st) {
+// f32 -> KV-cache blocks: contiguous destination, source rows of whole blocks with unit stride along dim 0 (what ggml_compute_forward_dup_f32 requires too)
+static int cpy_to_kv_blocks(const mi355q_tensor * a, const mi355q_tensor * dst, char * const * table, int index, hipStream_t st) {
     const int64_t n = nelements(dst);
-    const int bb = dst->type == MI355Q_TYPE_Q8_0 ? 34 : 18;     // (Q8_0 or Q4_0 blocks)
+    const int bb = kv_block_bytes_rt(dst->type);
     if (a->type != 0 || a->nb[0] != 4 || a->ne[0] % 32 != 0 || dst->ne[0] % 32 != 0 || dst->nb[0] != bb) return MI355Q_ERR_UNSUPPORTED;
     if (dst->nb[1] != dst->ne[0] / 32 * bb || dst->nb[2] != dst->nb[1] * dst->ne[1] || dst->nb[3] != dst->nb[2] * dst->ne[2]) return MI355Q_ERR_UNSUPPORTED;
     if (n == 0) return MI355Q_OK;
-    if (dst->type == MI355Q_TYPE_Q8_0) hipLaunchKernelGGL(k_cpy_f32_q8_0, dim3(grid_for(n / 4)), dim3(256), 0, st, to_d(a), (char *) dst->data, n / 32, table, index);
-    else                               hipLaunchKernelGGL(k_cpy_f32_q4_0, dim3(grid_for(n / 4)), dim3(256), 0, st, to_d(a), (char *) dst->data, n / 32, table, index);
+#define CPY_KVQ(T) hipLaunchKernelGGL(k_cpy_f32_kvq<T>, dim3(grid_for(n / 4)), dim3(256), 0, st, to_d(a), (char *) dst->data, n / 32, table, index)
+    switch (dst->type) {
+        case MI355Q_TYPE_Q8_0:   CPY_KVQ(MI355Q_TYPE_Q8_0); break;
+        case MI355Q_TYPE_Q4_0:   CPY_KVQ(MI355Q_TYPE_Q4_0); break;
+        case MI355Q_TYPE_Q4_1:   CPY_KVQ(MI355Q_TYPE_Q4_1); break;
+        case MI355Q_TYPE_Q5_0:   CPY_KVQ(MI355Q_TYPE_Q5_0); break;
+        case MI355Q_TYPE_Q5_1:   CPY_KVQ(MI355Q_TYPE_Q5_1); break;
+        case MI355Q_TYPE_IQ4_NL: CPY_KVQ(MI355Q_TYPE_IQ4_NL); break;
+        default: return MI355Q_ERR_UNSUPPORTED;
+    }
+#undef CPY_KVQ
     return MI355Q_OK;
 }
 
@@ -1123,8 +1137,8 @@ static bool cpy_type(int t) { return t == MI355Q_T_F32 || t == MI355Q_T_F16 || t
 
 int mi355q_op_cpy(const mi355q_tensor * a, const mi355q_tensor * dst, void * stream) {
     if (!a || !dst || nelements(a) != nelements(dst)) OPS_FAIL(MI355Q_ERR_SHAPE, "op_cpy: element counts differ");
-    if (dst->type == MI355Q_TYPE_Q8_0 || dst->type == MI355Q_TYPE_Q4_0) {
-        if (cpy_to_q8_0(a, dst, nullptr, 0, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 -> q8_0 / q4_0 needs a contiguous destination and source rows of whole 32-blocks");
+    if (kv_block_bytes_rt(dst->type)) {
+        if (cpy_to_kv_blocks(a, dst, nullptr, 0, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 -> q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl needs a contiguous destination and source rows of whole 32-blocks");
         OPS_LAUNCHED();
     }
     if (!cpy_type(a->type) || !cpy_type(dst->type)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy: f32 / f16 / bf16 only");
@@ -1137,8 +1151,8 @@ int mi355q_op_cpy(const mi355q_tensor * a, const mi355q_tensor * dst, void * str
 
 int mi355q_op_cpy_indirect(const mi355q_tensor * a, const mi355q_tensor * dst, void * const * dest_table, int index, void * stream) {
     if (!a || !dst || !dest_table || index < 0 || nelements(a) != nelements(dst)) OPS_FAIL(MI355Q_ERR_SHAPE, "op_cpy_indirect: arguments");
-    if (dst->type == MI355Q_TYPE_Q8_0 || dst->type == MI355Q_TYPE_Q4_0) {
-        if (cpy_to_q8_0(a, dst, (char * const *) dest_table, index, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 -> q8_0 / q4_0 needs a contiguous destination and source rows of whole 32-blocks");
+    if (kv_block_bytes_rt(dst->type)) {
+        if (cpy_to_kv_blocks(a, dst, (char * const *) dest_table, index, (hipStream_t) stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 -> q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl needs a contiguous destination and source rows of whole 32-blocks");
         OPS_LAUNCHED();
     }
     if (!cpy_type(a->type) || !cpy_type(dst->type)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_cpy_indirect: f32 / f16 / bf16 only");
@@ -1272,9 +1286,28 @@ int mi355q_op_rope(const mi355q_tensor * a, const int32_t * pos, const float * f
 
 int mi355q_op_mul_mat_f(const mi355q_tensor * a, const mi355q_tensor * b, const mi355q_tensor * dst, void * stream) {
     if (!a || !b || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_mul_mat_f: null tensor");
-    if ((a->type != 0 && a->type != 1 && a->type != MI355Q_T_BF16) || b->type != 0 || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: src0 f16/bf16/f32, src1 and dst f32");
+    const int kv_bb = kv_block_bytes_rt(a->type);               // (a view of a quantized KV cache: rows of <= 256 elements in whole blocks)
+    if ((a->type != 0 && a->type != 1 && a->type != MI355Q_T_BF16 && !kv_bb) || b->type != 0 || dst->type != 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: src0 f16/bf16/f32 or KV-cache blocks, src1 and dst f32");
     if (a->ne[0] != b->ne[0] || dst->ne[0] != a->ne[1] || dst->ne[1] != b->ne[1] || dst->ne[2] != b->ne[2] || dst->ne[3] != b->ne[3] ||
         a->ne[2] <= 0 || a->ne[3] <= 0 || b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3]) OPS_FAIL(MI355Q_ERR_SHAPE, "op_mul_mat_f: shapes");
+    if (kv_bb) {
+        if (a->nb[0] != kv_bb || b->nb[0] != 4 || dst->nb[0] != 4 || a->ne[0] % 32 || a->ne[0] > 256 || a->ne[0] < 32 || ((a->nb[1] | a->nb[2] | a->nb[3] | (int64_t) (uintptr_t) a->data) & 1))
+            OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: a KV-cache src0 needs rows of whole 32-blocks, at most 256 elements, contiguous, at even addresses");
+        if (b->ne[2] > 65535 || b->ne[3] > 65535 || b->ne[1] > 0x7FFFFFFF) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: too many rows / heads");
+        if (nelements(dst) == 0) return MI355Q_OK;
+        const dim3 g((unsigned) b->ne[1], (unsigned) b->ne[2], (unsigned) b->ne[3]);
+#define MM_KVQ(T) hipLaunchKernelGGL(k_mul_mat_kvq<T>, g, dim3(256), 0, (hipStream_t) stream, to_d(a), to_d(b), to_d(dst))
+        switch (a->type) {
+            case MI355Q_TYPE_Q8_0:   MM_KVQ(MI355Q_TYPE_Q8_0); break;
+            case MI355Q_TYPE_Q4_0:   MM_KVQ(MI355Q_TYPE_Q4_0); break;
+            case MI355Q_TYPE_Q4_1:   MM_KVQ(MI355Q_TYPE_Q4_1); break;
+            case MI355Q_TYPE_Q5_0:   MM_KVQ(MI355Q_TYPE_Q5_0); break;
+            case MI355Q_TYPE_Q5_1:   MM_KVQ(MI355Q_TYPE_Q5_1); break;
+            default:                 MM_KVQ(MI355Q_TYPE_IQ4_NL); break;
+        }
+#undef MM_KVQ
+        OPS_LAUNCHED();
+    }
     if (a->nb[0] != (a->type == 0 ? 4 : 2) || b->nb[0] != 4) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_mul_mat_f: the k dimension must be contiguous in both operands");
     const int64_t n_out = nelements(dst);
     if (n_out == 0) return MI355Q_OK;
@@ -1302,10 +1335,10 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
                              const mi355q_tensor * dst, float scale, float max_bias, float logit_softcap,
                              void * workspace, size_t workspace_bytes, void * stream) {
     if (!q || !k || !v || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: null tensor");
-    const bool kv_q80 = (k->type == MI355Q_TYPE_Q8_0 && v->type == MI355Q_TYPE_Q8_0) || (k->type == MI355Q_TYPE_Q4_0 && v->type == MI355Q_TYPE_Q4_0);     // a quantized cache
+    const bool kv_q80 = k->type == v->type && kv_block_bytes_rt(k->type) != 0;     // a quantized cache: both q8_0, q4_0, q4_1, q5_0, q5_1 or iq4_nl
     const bool kv_bf16 = k->type == MI355Q_T_BF16 && v->type == MI355Q_T_BF16;
-    const int  kv_bb = k->type == MI355Q_TYPE_Q4_0 ? 18 : 34;
-    if (q->type != 0 || !((k->type == 1 && v->type == 1) || kv_q80 || kv_bf16) || dst->type != 0 || (mask && mask->type != 1)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, k / v both f16, both bf16, both q8_0 or both q4_0, mask f16, dst f32");
+    const int  kv_bb = kv_block_bytes_rt(k->type);
+    if (q->type != 0 || !((k->type == 1 && v->type == 1) || kv_q80 || kv_bf16) || dst->type != 0 || (mask && mask->type != 1)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, k / v both f16, both bf16 or both of one of q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl, mask f16, dst f32");
     const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
     if (q->ne[0] != DK || v->ne[1] != n_kv || k->ne[2] <= 0 || v->ne[2] <= 0 || n_head % k->ne[2] || n_head % v->ne[2] || k->ne[3] <= 0 || v->ne[3] <= 0 ||
         nb3 % k->ne[3] || nb3 % v->ne[3] || dst->ne[0] != DV || dst->ne[1] != n_head || dst->ne[2] != N || dst->ne[3] != nb3)
@@ -1329,13 +1362,17 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
         const size_t kb16 = (size_t) DK * n_kv * k->ne[2] * k->ne[3] * 2, vb16 = (size_t) DV * n_kv * v->ne[2] * v->ne[3] * 2;
         if (workspace_bytes >= sc_bytes + ((kb16 + 255) & ~(size_t) 255) + vb16) {
             __half * kp = (__half *) ((char *) workspace + sc_bytes), * vp = (__half *) ((char *) kp + ((kb16 + 255) & ~(size_t) 255));
-            if (k->type == MI355Q_TYPE_Q8_0) {
-                hipLaunchKernelGGL(k_dequant_cache_f16<MI355Q_TYPE_Q8_0>, dim3(grid_for((int64_t) (kb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(k), kp);
-                hipLaunchKernelGGL(k_dequant_cache_f16<MI355Q_TYPE_Q8_0>, dim3(grid_for((int64_t) (vb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(v), vp);
-            } else {
-                hipLaunchKernelGGL(k_dequant_cache_f16<MI355Q_TYPE_Q4_0>, dim3(grid_for((int64_t) (kb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(k), kp);
-                hipLaunchKernelGGL(k_dequant_cache_f16<MI355Q_TYPE_Q4_0>, dim3(grid_for((int64_t) (vb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(v), vp);
+#define DEQ_KVQ(T) { hipLaunchKernelGGL(k_dequant_cache_f16<T>, dim3(grid_for((int64_t) (kb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(k), kp); \
+                     hipLaunchKernelGGL(k_dequant_cache_f16<T>, dim3(grid_for((int64_t) (vb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(v), vp); }
+            switch (k->type) {
+                case MI355Q_TYPE_Q8_0:   DEQ_KVQ(MI355Q_TYPE_Q8_0); break;
+                case MI355Q_TYPE_Q4_0:   DEQ_KVQ(MI355Q_TYPE_Q4_0); break;
+                case MI355Q_TYPE_Q4_1:   DEQ_KVQ(MI355Q_TYPE_Q4_1); break;
+                case MI355Q_TYPE_Q5_0:   DEQ_KVQ(MI355Q_TYPE_Q5_0); break;
+                case MI355Q_TYPE_Q5_1:   DEQ_KVQ(MI355Q_TYPE_Q5_1); break;
+                default:                 DEQ_KVQ(MI355Q_TYPE_IQ4_NL); break;
             }
+#undef DEQ_KVQ
             auto as16 = [](const mi355q_tensor * t, __half * p, mi355q_tensor & o) {
                 o = *t; o.data = p; o.type = 1; o.nb[0] = 2; o.nb[1] = 2 * t->ne[0]; o.nb[2] = o.nb[1] * t->ne[1]; o.nb[3] = o.nb[2] * t->ne[2];
             };
@@ -1351,14 +1388,18 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
     const bool mfma = N >= 16 && logit_softcap == 0.0f && workspace && workspace_bytes >= (size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4 &&
                       DK % 16 == 0 && DV % 16 == 0 && n_kv % 16 == 0 && al16(q) && al16(k) && al16(v) && n_head * nb3 <= 65535 && (!mask || mask->nb[1] == 2 * n_kv);
     if (kv_q80 || (kv_bf16 && !mfma)) {                      // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
-        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a q8_0 / q4_0 cache needs head sizes of whole 32-blocks; q8_0 / q4_0 / bf16 need n_kv <= 8192");
-        const size_t lds = (size_t) (2 * n_kv + (kv_bf16 ? DK : DK / 32 + DK / 4)) * 4;
+        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a quantized cache needs head sizes of whole 32-blocks; a quantized or bf16 cache needs n_kv <= 8192");
+        const size_t lds = (size_t) (2 * n_kv + (kv_bf16 ? DK : 2 * (DK / 32) + DK / 4)) * 4;
         static bool attr_q80[64] = {};
         if (lds > 48 * 1024) {
             int dev = 0; (void) hipGetDevice(&dev); dev = dev >= 0 && dev < 64 ? dev : 0;
             if (!attr_q80[dev]) {
                 if (hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q8_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
                     hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q4_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q4_1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q5_0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_Q5_1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_TYPE_IQ4_NL>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
                     hipFuncSetAttribute((const void *) k_flash_attn_ext_q80<MI355Q_T_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) OPS_FAIL(MI355Q_ERR_HIP, "op_flash_attn_ext: LDS attribute");
                 attr_q80[dev] = true;
             }
@@ -1366,12 +1407,19 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
         if (kv_bf16)
             hipLaunchKernelGGL(k_flash_attn_ext_q80<MI355Q_T_BF16>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream,
                                to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
-        else if (k->type == MI355Q_TYPE_Q8_0)
-            hipLaunchKernelGGL(k_flash_attn_ext_q80<MI355Q_TYPE_Q8_0>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream,
-                               to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
-        else
-            hipLaunchKernelGGL(k_flash_attn_ext_q80<MI355Q_TYPE_Q4_0>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream,
-                               to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2);
+        else {
+#define FA_KVQ(T) hipLaunchKernelGGL(k_flash_attn_ext_q80<T>, dim3((unsigned) N, (unsigned) n_head, (unsigned) nb3), dim3(FA_THREADS), lds, (hipStream_t) stream, \
+                               to_d(q), to_d(k), to_d(v), mask ? to_d(mask) : to_d(q), mask ? 1 : 0, to_d(dst), scale, max_bias, logit_softcap, m0, m1, n_head_log2)
+            switch (k->type) {
+                case MI355Q_TYPE_Q8_0:   FA_KVQ(MI355Q_TYPE_Q8_0); break;
+                case MI355Q_TYPE_Q4_0:   FA_KVQ(MI355Q_TYPE_Q4_0); break;
+                case MI355Q_TYPE_Q4_1:   FA_KVQ(MI355Q_TYPE_Q4_1); break;
+                case MI355Q_TYPE_Q5_0:   FA_KVQ(MI355Q_TYPE_Q5_0); break;
+                case MI355Q_TYPE_Q5_1:   FA_KVQ(MI355Q_TYPE_Q5_1); break;
+                default:                 FA_KVQ(MI355Q_TYPE_IQ4_NL); break;
+            }
+#undef FA_KVQ
+        }
         OPS_LAUNCHED();
     }
     {

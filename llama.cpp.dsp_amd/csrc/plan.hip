@@ -63,7 +63,7 @@ struct AttnStage {
     int kv_lds;                                    // the split's K / V window fits the LDS: plan_attn_lds runs the stage
     int fa_seq;                                    // rows-per-position V cache, window in one workgroup: the CPU's sequential f16 accumulation (plan_attn_lds)
     int entry_barrier;                             // the previous stage is not a GEMV: its last LDS reads must be fenced off
-    int kv_type, kv_rb, kv_unit;                   // quantized cache (plan_attn_q80): MI355Q_TYPE_Q8_0 / _Q4_0 (0: f16), bytes per head row, bytes per copy unit (2, 4, 8)
+    int kv_type, kv_rb, kv_unit;                   // quantized cache (plan_attn_q80): MI355Q_TYPE_Q8_0 / _Q4_0 / _Q4_1 / _Q5_0 / _Q5_1 / _IQ4_NL (0: f16), bytes per head row, bytes per copy unit (2, 4, 8)
     float scale;
     // rope (ggml_rope_cache_init; see ops_glue.hip k_rope)
     int n_dims, neox; float freq_scale, ext_factor, attn_factor, theta_scale, corr0, corr1;
@@ -1291,10 +1291,10 @@ static __device__ __noinline__ bool plan_attn_lds(AttnC a_in, const StageCtx & c
     return true;
 }
 
-// ---- attention of one token over a Q8_0 / Q4_0 cache, K / V window in LDS ----------------------------------------------------------------------
+// ---- attention of one token over a quantized cache (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL), K / V window in LDS ----------------------------------------------------------------------
 // The flash layout only (rows per position).  Workgroup = (head h, KV split sp), as plan_attn_lds.  The per-position arithmetic is
 // k_flash_attn_ext_q80's (fa_quant.cuh, shared): q roped in f32 and quantized to Q8_0, scores by the CPU's block dot, the online softmax in position
-// order, V dequantized into an F32 accumulator.  This token's K / V rows are quantized with CPY f32 -> q8_0 / q4_0's arithmetic into the cache AND
+// order, V dequantized into an F32 accumulator.  This token's K / V rows are quantized with CPY f32 -> type's arithmetic into the cache AND
 // into the LDS window, so that its own position is read back from the blocks as the CPU reads it.  One split: the output is k_flash_attn_ext_q80's,
 // bit for bit.  Several: each split publishes (its F32 accumulator, its maximum, its sum S) and plan_attn_combine merges them.
 //   0  polls of q / k / v | rope table and cache slot | window copy (2 x cnt rows of hd / 32 blocks: 2-, 4- or 8-byte units) and the mask
@@ -1339,7 +1339,7 @@ static __device__ __noinline__ bool plan_attn_q80(AttnC a_in, const StageCtx & c
     const int h = (int) blockIdx.x / n_split, sp = (int) blockIdx.x % n_split, gq = a->n_head / a->n_head_kv, g = h / gq;
     const int half = hd >> 1, per_pad = (a->per + 31) & ~31, rb = a->kv_rb, nblk = hd >> 5;
     // LDS (inside the staging area; every area a multiple of 16 bytes)
-    float * misc = c.stg;                                                      // [16]: 0 maximum, 2 cache slot (int)
+    float * misc = c.stg;                                                      // [16]: 0 maximum, 2 cache slot (int), 8..15 q's block sums (Q8_1: a Q4_1 / Q5_1 cache)
     float * sq = misc + 16, * sk = sq + hd, * sv = sk + hd, * cst = sv + hd;   // q / k / v as polled (q, k roped in place) | cos [hd/2] sin [hd/2]
     float * qd = cst + hd;                                                     // [8] q's block scales
     uint32_t * qq = (uint32_t *) (qd + 8);                                     // [64] q's packed quants
@@ -1450,17 +1450,17 @@ static __device__ __noinline__ bool plan_attn_q80(AttnC a_in, const StageCtx & c
     // ---- 2. q -> Q8_0 for the scores; this token's K / V rows -> blocks: into the cache (one workgroup per kv head) and into the window ----
     const int slot = ((const int *) misc)[2];
     const bool in_win = slot >= j0 && slot < j1, store = sp == 0 && h % gq == 0;
-    if (wave == 0) fa_quantize_q(sq, lane, hd, qq, qd);
+    if (wave == 0) fa_quantize_q<kv_has_min<KVT>()>(sq, lane, hd, qq, qd, misc + 8);
     else if (wave == 1 || wave == 2) {
         const float * x = wave == 1 ? sk : sv;
         const int e = 4 * lane;
         const float4 v4 = e < hd ? make_float4(x[e], x[e + 1], x[e + 2], x[e + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        uint32_t w; float d;
-        kv_quant_group8<KVT>(v4, w, d);
+        KvBlk o;
+        kv_quant_group8<KVT>(v4, o);
         if (e < hd) {
             const int off = BB * (lane >> 3), l8 = lane & 7;
-            if (in_win) kv_store_group8<KVT>((wave == 1 ? kwin : vwin) + (size_t) (slot - j0) * rb + off, l8, w, d);
-            if (store)  kv_store_group8<KVT>((wave == 1 ? kdst : vdst) + (int64_t) g * rb + off, l8, w, d);
+            if (in_win) kv_store_group8<KVT>((wave == 1 ? kwin : vwin) + (size_t) (slot - j0) * rb + off, l8, o);
+            if (store)  kv_store_group8<KVT>((wave == 1 ? kdst : vdst) + (int64_t) g * rb + off, l8, o);
         }
     }
     plan_lds_barrier();
@@ -1468,7 +1468,7 @@ static __device__ __noinline__ bool plan_attn_q80(AttnC a_in, const StageCtx & c
     // ---- 3. scores: one position per thread (a masked position stays -inf whatever its cache blocks hold) ----
     for (int jj = tid; jj < cnt; jj += GEMV_THREADS) {
         const float m = sc[jj];
-        sc[jj] = m == -INFINITY ? -INFINITY : __fadd_rn(__fmul_rn(fa_dot_q80<KVT>(kwin + (size_t) jj * rb, qd, qq, nblk), scale_r), m);
+        sc[jj] = m == -INFINITY ? -INFINITY : __fadd_rn(__fmul_rn(fa_dot_q80<KVT>(kwin + (size_t) jj * rb, qd, qq, nblk, misc + 8), scale_r), m);
     }
     plan_lds_barrier();
     PLAN_STAMP(3);
@@ -1610,9 +1610,16 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
             }
         } else if (kind == PLAN_K_ATTN) {
             const int af = st->flags;
-            if (af & PLAN_F_ATTN_Q)
-                ok = ((AttnC) st->attn)->kv_type == MI355Q_TYPE_Q8_0 ? plan_attn_q80<MI355Q_TYPE_Q8_0>((AttnC) st->attn, c, epoch + st->tag_off)
-                                                                     : plan_attn_q80<MI355Q_TYPE_Q4_0>((AttnC) st->attn, c, epoch + st->tag_off);
+            if (af & PLAN_F_ATTN_Q) {
+                switch (((AttnC) st->attn)->kv_type) {
+                case MI355Q_TYPE_Q8_0: ok = plan_attn_q80<MI355Q_TYPE_Q8_0>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                case MI355Q_TYPE_Q4_0: ok = plan_attn_q80<MI355Q_TYPE_Q4_0>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                case MI355Q_TYPE_Q4_1: ok = plan_attn_q80<MI355Q_TYPE_Q4_1>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                case MI355Q_TYPE_Q5_0: ok = plan_attn_q80<MI355Q_TYPE_Q5_0>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                case MI355Q_TYPE_Q5_1: ok = plan_attn_q80<MI355Q_TYPE_Q5_1>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                default:               ok = plan_attn_q80<MI355Q_TYPE_IQ4_NL>((AttnC) st->attn, c, epoch + st->tag_off); break;
+                }
+            }
             else ok = (af & PLAN_F_ATTN_LDS) ? plan_attn_lds((AttnC) st->attn, c, epoch + st->tag_off) : plan_attn((AttnC) st->attn, c, epoch + st->tag_off);
         } else {
             ok = plan_attn_combine((AttnC) st->attn, c, epoch + st->tag_off);
@@ -1623,6 +1630,9 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
 
 // ------------------------------------------------------------------------------------------------
 // host side
+static const char * plan_kv_name(int t) {
+    return t == MI355Q_TYPE_Q8_0 ? "q8_0" : t == MI355Q_TYPE_Q4_0 ? "q4_0" : t == MI355Q_TYPE_Q4_1 ? "q4_1" : t == MI355Q_TYPE_Q5_0 ? "q5_0" : t == MI355Q_TYPE_Q5_1 ? "q5_1" : "iq4_nl";
+}
 // ------------------------------------------------------------------------------------------------
 struct Plan {
     int           device = 0, n_cu = 0, grid = 0, n_stages = 0, even = 0;
@@ -1745,10 +1755,12 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             if (at->n_head < 1 || at->n_head_kv < 1 || at->n_head % at->n_head_kv || at->head_dim < 32 || at->head_dim > 256 || at->head_dim % 32 || at->n_kv < 1) { mi355q_set_error("plan_create: attn stage: bad head geometry"); return MI355Q_ERR_SHAPE; }
             if (at->rope.mode != 0 && at->rope.mode != 2) { mi355q_set_error("plan_create: attn stage: rope mode must be 0 or 2"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->rope.n_dims <= 0 || at->rope.n_dims % 2 || at->rope.n_dims > at->head_dim) { mi355q_set_error("plan_create: attn stage: rope n_dims"); return MI355Q_ERR_SHAPE; }
-            const int kvq = in.flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0);
-            if (kvq == (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0)) { mi355q_set_error("plan_create: attn stage: KV_Q8_0 and KV_Q4_0 both set"); return MI355Q_ERR_UNSUPPORTED; }
-            const int kv_bb = kvq == MI355Q_STAGE_KV_Q8_0 ? 34 : 18;
-            if (kvq && at->v_nb_dim != kv_bb) { mi355q_set_error("plan_create: attn stage: a q8_0 / q4_0 cache needs the flash layout (V rows per position, v_nb_dim = block bytes); the transposed V cache is not supported"); return MI355Q_ERR_UNSUPPORTED; }
+            const int kvq = in.flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL);
+            if (kvq & (kvq - 1)) { mi355q_set_error("plan_create: attn stage: more than one MI355Q_STAGE_KV_* flag set"); return MI355Q_ERR_UNSUPPORTED; }
+            const int kv_type = kvq == MI355Q_STAGE_KV_Q8_0 ? MI355Q_TYPE_Q8_0 : kvq == MI355Q_STAGE_KV_Q4_0 ? MI355Q_TYPE_Q4_0 : kvq == MI355Q_STAGE_KV_Q4_1 ? MI355Q_TYPE_Q4_1 :
+                                kvq == MI355Q_STAGE_KV_Q5_0 ? MI355Q_TYPE_Q5_0 : kvq == MI355Q_STAGE_KV_Q5_1 ? MI355Q_TYPE_Q5_1 : kvq == MI355Q_STAGE_KV_IQ4_NL ? MI355Q_TYPE_IQ4_NL : 0;
+            const int kv_bb = kv_block_bytes_rt(kv_type);
+            if (kvq && at->v_nb_dim != kv_bb) { mi355q_set_error("plan_create: attn stage: a quantized cache needs the flash layout (V rows per position, v_nb_dim = block bytes); the transposed V cache is not supported"); return MI355Q_ERR_UNSUPPORTED; }
             if (!kvq && at->v_nb_dim != 2 && at->v_nb_pos != 2) { mi355q_set_error("plan_create: attn stage: V cache must be contiguous along head_dim or along positions"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->n_head > n_cu) { mi355q_set_error("plan_create: attn stage: more heads than CUs"); return MI355Q_ERR_UNSUPPORTED; }
             AttnStage A = {};
@@ -1759,11 +1771,11 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             A.k_dst = (char * const *) at->k_dst; A.v_dst = (char * const *) at->v_dst; A.mask = (const char *) at->mask; A.mask_f16 = at->mask_f16;
             A.n_head = at->n_head; A.n_head_kv = at->n_head_kv; A.hd = hd; A.n_kv = at->n_kv; A.scale = at->scale;
             if (kvq) {                                         // a quantized cache: rows of hd / 32 blocks, copied into LDS in the widest unit every address allows
-                A.kv_type = kvq == MI355Q_STAGE_KV_Q8_0 ? MI355Q_TYPE_Q8_0 : MI355Q_TYPE_Q4_0; A.kv_rb = hd / 32 * kv_bb;
+                A.kv_type = kv_type; A.kv_rb = hd / 32 * kv_bb;
                 const uint64_t any = (uint64_t) (uintptr_t) at->k_cache | (uint64_t) (uintptr_t) at->v_cache | (uint64_t) at->k_nb_pos | (uint64_t) at->k_nb_head |
                                      (uint64_t) at->v_nb_pos | (uint64_t) at->v_nb_head | (uint64_t) A.kv_rb;
                 A.kv_unit = (any & 7) == 0 ? 8 : (any & 3) == 0 ? 4 : 2;
-                if (any & 1) { mi355q_set_error("plan_create: attn stage: q8_0 / q4_0 cache addresses and strides must be even"); return MI355Q_ERR_UNSUPPORTED; }
+                if (any & 1) { mi355q_set_error("plan_create: attn stage: the addresses and strides of a quantized cache must be even"); return MI355Q_ERR_UNSUPPORTED; }
             }
             // KV splits per head: one workgroup per 256 positions, at most #CU / n_head.  A window of <= 256 positions is ONE workgroup per head and
             // needs no merge stage (a dependent hop costs more than reading 256 cache rows).
@@ -1930,18 +1942,18 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             A.entry_barrier = si == 0 || v[si - 1].kind != PLAN_K_GEMV;
             if (A.kv_type) {
                 // a quantized cache always runs from LDS (plan_attn_q80): 21 hd + 352 bytes of vectors, 8 bytes of scores per position and the K / V
-                // windows of 2 x rb bytes per position (rb = hd / 32 x 34 or 18).  A window beyond that is refused: the caller falls back to the node ops.
+                // windows of 2 x rb bytes per position (rb = hd / 32 x the type's block bytes: 34, 18, 20, 22, 24, 18).  A window beyond that is refused: the caller falls back to the node ops.
                 const size_t need = (size_t) 4 * (16 + 4 * A.hd + 72) + (size_t) 8 * per_pad + (size_t) 2 * per_pad * A.kv_rb + 64;
                 if (fixed + ((std::max(need, stg_max) + 15) & ~(size_t) 15) > cap) {
                     const size_t room = cap - fixed - 64 - (size_t) 4 * (16 + 4 * A.hd + 72);
                     char msg[200];
                     snprintf(msg, sizeof(msg), "plan_create: attn stage: a %s KV window of %d positions per split (%d split(s)) does not fit the LDS: at most %zu positions per split",
-                             A.kv_type == MI355Q_TYPE_Q8_0 ? "q8_0" : "q4_0", A.per, A.n_split, (room / (8 + 2 * (size_t) A.kv_rb)) & ~(size_t) 31);
+                             plan_kv_name(A.kv_type), A.per, A.n_split, (room / (8 + 2 * (size_t) A.kv_rb)) & ~(size_t) 31);
                     mi355q_set_error(msg);
                     return MI355Q_ERR_UNSUPPORTED;
                 }
                 v[si].flags |= PLAN_F_ATTN_Q; if (need > stg_max) stg_max = need;
-                if (getenv("MI355Q_PLAN_VERBOSE")) fprintf(stderr, "mi355q plan: attention stage %zu: n_kv %d, %d split(s) of %d positions, %s cache, window in LDS (%zu bytes, %zu fixed, %d-byte copies)\n", si, A.n_kv, A.n_split, A.per, A.kv_type == MI355Q_TYPE_Q8_0 ? "q8_0" : "q4_0", need, fixed, A.kv_unit);
+                if (getenv("MI355Q_PLAN_VERBOSE")) fprintf(stderr, "mi355q plan: attention stage %zu: n_kv %d, %d split(s) of %d positions, %s cache, window in LDS (%zu bytes, %zu fixed, %d-byte copies)\n", si, A.n_kv, A.n_split, A.per, plan_kv_name(A.kv_type), need, fixed, A.kv_unit);
                 continue;
             }
             const size_t need = (size_t) 50 * A.hd + 64 + (size_t) 8 * per_pad + (size_t) 4 * per_pad * A.hd + (size_t) 16 * per_pad + 64;     // (plan_attn_lds: 12.5 hd + 16 + 2 per floats, K rows of hd + 8 f16, V)

@@ -38,8 +38,8 @@ int mi355q_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int n_st
     static const int want_ring = [] { const char * e = getenv("MI355Q_PLAN_ENGINE"); return e && strcmp(e, "ring") == 0 ? 1 : 0; }();
     if (want_ring && stages)                                   // plan_ring.hip has no quantized-cache attention stage: it would read the blocks as f16
         for (int i = 0; i < n_stages; ++i)
-            if (stages[i].kind == MI355Q_STAGE_ATTN && (stages[i].flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0))) {
-                mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for a q8_0 / q4_0 KV cache"); return MI355Q_ERR_UNSUPPORTED;
+            if (stages[i].kind == MI355Q_STAGE_ATTN && (stages[i].flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL))) {
+                mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for a quantized (q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl) KV cache"); return MI355Q_ERR_UNSUPPORTED;
             }
     mi355q_plan * impl = nullptr;
     const int rc = want_ring ? mi355q_ring_plan_create(&impl, stages, n_stages, flags) : mi355q_regs_plan_create(&impl, stages, n_stages, flags);

@@ -302,7 +302,8 @@ def mul_mat_multi(ws_: list, x, outs=None, flags: int = 0):
     return ys
 
 
-_STAGE_KV = {"f16": 0, "q8_0": 0x4, "q4_0": 0x8}           # mi355q_stage.flags of an ATTN stage: MI355Q_STAGE_KV_Q8_0 / MI355Q_STAGE_KV_Q4_0
+_STAGE_KV = {"f16": 0, "q8_0": 0x4, "q4_0": 0x8, "q4_1": 0x10, "q5_0": 0x20, "q5_1": 0x40, "iq4_nl": 0x80}     # mi355q_stage.flags of an ATTN stage: MI355Q_STAGE_KV_*
+KV_BLOCK = {"q8_0": (34, Q8_0), "q4_0": (18, Q4_0), "q4_1": (20, Q4_1), "q5_0": (22, Q5_0), "q5_1": (24, Q5_1), "iq4_nl": (18, IQ4_NL)}     # cache type -> (bytes per 32-element block, type id)
 
 
 class Plan:
@@ -317,7 +318,7 @@ class Plan:
                        attn_factor=1.0, beta_fast=32.0, beta_slow=1.0), freq_factors=None, k_cache=, v_cache=, k_nb_pos=, k_nb_head=, v_nb_pos=,
                        v_nb_dim=, v_nb_head=, k_dst=, v_dst= (int64 device tensors holding the destination ADDRESSES), v_dst_nb=, mask=None,
                        n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16"), no_plain=False)       -- see include/mi355q.h mi355q_attn;
-        kv="q8_0" / "q4_0": the caches hold blocks of that type (uint8 tensors; MI355Q_STAGE_KV_Q8_0 / _Q4_0, flash layout only).
+        kv="q8_0" / "q4_0" / "q4_1" / "q5_0" / "q5_1" / "iq4_nl": the caches hold blocks of that type (uint8 tensors; MI355Q_STAGE_KV_*, flash layout only).
     The tensors are referenced by address: keep them alive (the Plan holds references) and do not move them."""
 
     def __init__(self, stages, flags: int = 0):
@@ -424,10 +425,12 @@ def _td(t) -> _Tensor:
 
 
 def _td_q8_0(t, kv: str = "q8_0") -> _Tensor:
-    """uint8 torch tensor holding contiguous block_q8_0 (34-byte) or block_q4_0 (18-byte) rows, shape [..., n / 32 * bb] (<= 4 dims) -> mi355q_tensor of
-    that type with ne[0] = n."""
+    """uint8 torch tensor holding contiguous block rows of the cache type `kv` (KV_BLOCK: 34-byte block_q8_0, 18-byte block_q4_0, ...), shape
+    [..., n / 32 * bb] (<= 4 dims) -> mi355q_tensor of that type with ne[0] = n."""
     torch = _torch()
-    bb, code = (34, 8) if kv == "q8_0" else (18, 2)
+    if kv not in KV_BLOCK:
+        raise ValueError(f"kv must be one of {sorted(KV_BLOCK)}, not {kv!r}")
+    bb, code = KV_BLOCK[kv]
     assert t.dtype == torch.uint8 and t.is_contiguous() and 1 <= t.dim() <= 4 and t.shape[-1] % bb == 0
     shape = list(t.shape)[::-1] + [1] * (4 - t.dim())
     d = _Tensor(); d.data = t.data_ptr(); d.type = code
@@ -485,14 +488,14 @@ def op_unary_mul(uop: int, a, b):
 
 def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0"):
     """GGML_OP_FLASH_ATTN_EXT: q f32 [B, H, N, DK] (torch order), k f16 [Bk, Hk, n_kv, DK], v f16 [Bv, Hv, n_kv, DV], mask f16 [>= N, >= n_kv]
-    or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 cache)."""
+    or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl cache)."""
     torch = _torch()
     out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3]), dtype=torch.float32, device=q.device)
     ws, wsb = (_workspace(torch, int(lib().mi355q_op_flash_attn_ext_workspace(v.shape[3], q.shape[2], q.shape[1], q.shape[0], k.shape[2])), q.device)
                if split else (None, 0))
     tdkv = (lambda t: _td_q8_0(t, kv)) if k.dtype == torch.uint8 else _td      # (uint8: block_q8_0 / block_q4_0 rows, a quantized cache)
     if k.dtype == torch.uint8:
-        out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3] // (34 if kv == "q8_0" else 18) * 32), dtype=torch.float32, device=q.device)
+        out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3] // KV_BLOCK[kv][0] * 32), dtype=torch.float32, device=q.device)
     _check(lib().mi355q_op_flash_attn_ext(C.byref(_td(q)), C.byref(tdkv(k)), C.byref(tdkv(v)), C.byref(_td(mask)) if mask is not None else None,
                                           C.byref(_td(out)), scale, max_bias, logit_softcap, ws.data_ptr() if ws is not None else None, wsb,
                                           _stream(torch)), "op_flash_attn_ext")
@@ -500,7 +503,8 @@ def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_
 
 
 def op_cpy(a, out, kv: str = "q8_0"):
-    """GGML_OP_CPY among f32 / f16 / bf16 tensors; a uint8 `out` of shape [..., n / 32 * 34] (kv "q8_0") or [..., n / 32 * 18] ("q4_0") is a quantized destination (KV cache rows)."""
+    """GGML_OP_CPY among f32 / f16 / bf16 tensors; a uint8 `out` of shape [..., n / 32 * bb] (bb = KV_BLOCK[kv][0]: 34 for "q8_0", 18 "q4_0", 20 "q4_1", 22 "q5_0", 24 "q5_1", 18 "iq4_nl") is a
+    quantized destination (KV cache rows)."""
     td_out = _td_q8_0(out, kv) if out.dtype == _torch().uint8 else _td(out)
     _check(lib().mi355q_op_cpy(C.byref(_td(a)), C.byref(td_out), _stream(_torch())), "op_cpy")
     return out
@@ -573,12 +577,14 @@ def op_scale(a, scale: float, out=None):
     return out
 
 
-def op_mul_mat_f(a, b, out=None):
-    """GGML_OP_MUL_MAT with an f16/bf16/f32 src0: a [.., M, K], b [.., N, K] (torch order) -> [.., N, M] f32."""
+def op_mul_mat_f(a, b, out=None, kv: str = "q8_0"):
+    """GGML_OP_MUL_MAT with an f16/bf16/f32 src0: a [.., M, K], b [.., N, K] (torch order) -> [.., N, M] f32.  A uint8 `a` holds rows of KV-cache
+    blocks of type `kv` ([.., M, K / 32 * bb], K <= 256): the KQ product of a non-flash graph over a quantized K cache, with the CPU's vec_dot."""
     torch = _torch()
     if out is None:
         out = torch.empty(tuple(b.shape[:-2]) + (b.shape[-2], a.shape[-2]), dtype=torch.float32, device=b.device)
-    _check(lib().mi355q_op_mul_mat_f(C.byref(_td(a)), C.byref(_td(b)), C.byref(_td(out)), _stream(torch)), "op_mul_mat_f")
+    td_a = _td_q8_0(a, kv) if a.dtype == torch.uint8 else _td(a)
+    _check(lib().mi355q_op_mul_mat_f(C.byref(td_a), C.byref(_td(b)), C.byref(_td(out)), _stream(torch)), "op_mul_mat_f")
     return out
 
 
