@@ -43,7 +43,8 @@ static bool mi355_plan_mat(const struct ggml_tensor * n) {          // a quantiz
     if (w->ne[2] != 1 || w->ne[3] != 1 || mi355_root(w)->ne[0] != w->ne[0] || w->nb[0] != ggml_type_size(w->type)) return false;
     if (mi355q_weights_are_planar((int) w->type, w->ne[0]) != 1 || mi355_q80_canonical(w) || (w->nb[1] % 16) || ((uintptr_t) w->data % 16)) return false;
     switch (w->type) {                                       // (which mixes of these have a kernel instantiation is mi355q_plan_create's call: a refusal declines the plan)
-    case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS: return true;
+    case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
+    case GGML_TYPE_IQ3_S: case GGML_TYPE_IQ3_XXS: return true;
     default: return false;
     }
 }

@@ -143,8 +143,11 @@ static size_t moe_grouped_workspace(int type, int64_t m, int64_t k, int64_t pair
     const int64_t slots = moe_slots(type, k, pairs, n_expert);
     return (size_t) (moe_align256(4 * (slots + pairs + n_expert + slots / 64)) + moe_align256(4 * slots * k)) + mi355q_mul_mat_workspace(type, m, slots, k);
 }
+// (planar IQ3_S / IQ3_XXS rows are NOT grouped: MUL_MAT_ID keeps the CPU's integer arithmetic for them at every pair count -- one streamed GEMV
+//  column per pair with the ids read on the device -- where the grouped form would answer with the bf16 tier's rounding)
+static bool moe_grouped_type(int type) { return type != MI355Q_TYPE_IQ3_S && type != MI355Q_TYPE_IQ3_XXS; }
 static bool moe_grouped_ok(int type, int64_t m, int64_t k, const void * x, int64_t x_stride1, int64_t x_stride2) {
-    return mmq_supported(type, k) && m % 4 == 0 && k % 4 == 0 && !(((uintptr_t) x | (uintptr_t) x_stride1 | (uintptr_t) x_stride2) & 15);
+    return moe_grouped_type(type) && mmq_supported(type, k) && m % 4 == 0 && k % 4 == 0 && !(((uintptr_t) x | (uintptr_t) x_stride1 | (uintptr_t) x_stride2) & 15);
 }
 // canonical rows: the grouped form runs on the batched canonical tier
 static bool moe_grouped_canonical_ok(const TypeInfo * t, int type, int64_t k, const void * x, int64_t x_stride1, int64_t x_stride2) {
@@ -421,7 +424,7 @@ int mi355q_mul_mat(int type, const void * w, int64_t w_stride, const float * x, 
 size_t mi355q_mul_mat_id_workspace(int type, int64_t m, int64_t k, int64_t n_used, int64_t n_tok, int64_t x_ne1, int64_t n_expert) {
     const TypeInfo * t = type_info(type);
     if (!t || t->act < 0 || k % t->blck) return 0;
-    const size_t grouped = n_used * n_tok >= MOE_GROUPED_MIN_PAIRS && ((is_planar(t, k) && mmq_supported(type, k) && m % 4 == 0) || (!is_planar(t, k) && mmq_generic_supported(type, k))) ? moe_grouped_workspace(type, m, k, n_used * n_tok, n_expert < 1 ? 1 : (n_expert > 1024 ? 1024 : n_expert)) : 0;
+    const size_t grouped = n_used * n_tok >= MOE_GROUPED_MIN_PAIRS && ((is_planar(t, k) && moe_grouped_type(type) && mmq_supported(type, k) && m % 4 == 0) || (!is_planar(t, k) && mmq_generic_supported(type, k))) ? moe_grouped_workspace(type, m, k, n_used * n_tok, n_expert < 1 ? 1 : (n_expert > 1024 ? 1024 : n_expert)) : 0;
     if (is_planar(t, k)) return grouped;
     const size_t generic = (size_t) align256(mi355q_row_size(t->act, k) * n_tok * x_ne1);
     return grouped > generic ? grouped : generic;

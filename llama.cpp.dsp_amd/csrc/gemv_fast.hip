@@ -140,7 +140,7 @@ struct Streamer {
 #pragma unroll
         for (int d = 0; d < D; ++d) issue(ring[d], a, w_off, lane);
     }
-    __device__ __forceinline__ void run(const GemvArgs & a, const ActView * av, int lane, int64_t w_off, int64_t y_off) {
+    __device__ __forceinline__ void run(const GemvArgs & a, const ActView * av, const uint32_t * grid, int lane, int64_t w_off, int64_t y_off) {
         float acc[NCOLS];
 #pragma unroll
         for (int n = 0; n < NCOLS; ++n) acc[n] = 0.0f;
@@ -148,7 +148,7 @@ struct Streamer {
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 if (cs_gr < r_hi) {                           // wave-uniform
-                    if (64 * cs_s + lane < nchunks) Consume<T, NCOLS>::run(ring[d], cs_s, lane, av, acc);
+                    if (64 * cs_s + lane < nchunks) Consume<T, NCOLS>::run(ring[d], cs_s, lane, av, acc, grid);
                     if (++cs_s == steps) {                    // row finished: reduce, store, next row
 #pragma unroll
                         for (int n = 0; n < NCOLS; ++n) {
@@ -207,10 +207,19 @@ k_gemv_fast(const GemvArgs a) {
     const float4 c0 = act_fetch((const float *) xbase, wave, k, a.x_vec, lane);
     const float4 c1 = act_fetch((const float *) xbase, wave + GEMV_WAVES, k, a.x_vec, lane);
     st.prime(a, r_begin, r_end, k, wave, lane, w_off, y_off);              // first D items in flight ...
+    // IQ3_S / IQ3_XXS: the type's code book sits behind the activation image, one word per thread.  Its load is issued LAST, behind the
+    // activation and weight loads, and its word is stored only after the prologue, which drains every load anyway: nothing waits for it alone.
+    uint32_t * const grid = type_is_iq3(WT) ? (uint32_t *) (lds + NCOLS * colb) : nullptr;
+    uint32_t grid_word = 0;
+    if constexpr (type_is_iq3(WT)) if ((int) threadIdx.x < iq3_grid_words(WT)) grid_word = iq3_grid_word<WT>((int) threadIdx.x);
     MI355Q_STAMP(2);
     quantize_columns_to_lds<FAM, NCOLS, ROUND_EVEN>(lds, colb, xbase, a.x_stride, k, a.x_vec, wave, lane, c0, c1);   // ... while the activations are quantized
+    if constexpr (type_is_iq3(WT)) {
+        if ((int) threadIdx.x < iq3_grid_words(WT)) grid[threadIdx.x] = grid_word;
+        __syncthreads();
+    }
     MI355Q_STAMP(3);
-    st.run(a, av, lane, w_off, y_off);
+    st.run(a, av, grid, lane, w_off, y_off);
     MI355Q_STAMP(5);
 }
 
@@ -219,7 +228,8 @@ k_gemv_fast(const GemvArgs a) {
 // ------------------------------------------------------------------------------------------------
 static int family_of(int type) {
     switch (type) {
-    case MI355Q_TYPE_Q4_K: case MI355Q_TYPE_Q5_K: case MI355Q_TYPE_Q6_K: case MI355Q_TYPE_IQ4_XS: return FAM_Q8K;
+    case MI355Q_TYPE_Q4_K: case MI355Q_TYPE_Q5_K: case MI355Q_TYPE_Q6_K: case MI355Q_TYPE_IQ4_XS:
+    case MI355Q_TYPE_IQ3_S: case MI355Q_TYPE_IQ3_XXS: return FAM_Q8K;
     case MI355Q_TYPE_Q8_0: case MI355Q_TYPE_Q4_0: case MI355Q_TYPE_IQ4_NL: return FAM_Q80;
     default: return -1;
     }
@@ -232,7 +242,7 @@ int gemv_fast_max_cols(int type, int64_t k) {
     const int fam = family_of(type);
     if (fam < 0) return 0;
     const int colb = (lds_col_bytes(fam, (int) k) + 15) & ~15;
-    const int n = (160 * 1024 - 1024) / colb;
+    const int n = (160 * 1024 - 1024 - iq3_grid_bytes(type)) / colb;
     return n > 8 ? 8 : n;
 }
 
@@ -340,7 +350,7 @@ static int launch_gemv_fast_typed(const mi355q_mat * mats, int n_mats, const flo
     grid = (rows + rpw - 1) / rpw;
     a.rows_per_wg = rpw;
     const int colb = (lds_col_bytes(fam, (int) k) + 15) & ~15;
-    const size_t lds_bytes = (size_t) colb * ncols;
+    const size_t lds_bytes = (size_t) colb * ncols + (size_t) iq3_grid_bytes(mats[0].type);
     const bool even = (flags & MI355Q_FLAG_ROUND_EVEN) != 0;
     const dim3 g((unsigned) grid, (unsigned) pairs);
     const int wt = mats[0].type;                               // the caller groups by type
@@ -349,6 +359,8 @@ static int launch_gemv_fast_typed(const mi355q_mat * mats, int n_mats, const flo
         case MI355Q_TYPE_Q4_K: return launch_cols<FAM_Q8K, MI355Q_TYPE_Q4_K, false>(a, ncols, g, lds_bytes, stream);
         case MI355Q_TYPE_Q6_K: return launch_cols<FAM_Q8K, MI355Q_TYPE_Q6_K, false>(a, ncols, g, lds_bytes, stream);
         case MI355Q_TYPE_IQ4_XS: return launch_cols<FAM_Q8K, MI355Q_TYPE_IQ4_XS, false>(a, ncols, g, lds_bytes, stream);
+        case MI355Q_TYPE_IQ3_S: return launch_cols<FAM_Q8K, MI355Q_TYPE_IQ3_S, false>(a, ncols, g, lds_bytes, stream);
+        case MI355Q_TYPE_IQ3_XXS: return launch_cols<FAM_Q8K, MI355Q_TYPE_IQ3_XXS, false>(a, ncols, g, lds_bytes, stream);
         default:               return launch_cols<FAM_Q8K, MI355Q_TYPE_Q5_K, false>(a, ncols, g, lds_bytes, stream);
         }
     }

@@ -4,6 +4,7 @@
 // activation-quantization prologue.
 #pragma once
 #include "act_quant.cuh"
+#include "iq_tables.h"   // code books of IQ3_S / IQ3_XXS, copied into LDS once per workgroup (iq3_grid_to_lds)
 
 namespace mi355q {
 
@@ -18,7 +19,7 @@ constexpr int GEMV_MAX_MATS = 4;
 //   Q8_0 family: q8[k] | d f32 [k/32] (already f16-rounded) | sums i32 [k/32]
 // ------------------------------------------------------------------------------------------------
 // kernel families: which weight types one kernel instantiation can stream (they share the activation image)
-//   FAM_Q8K : Q4_K, Q5_K, Q6_K, IQ4_XS (Q8_K activations)   FAM_Q80 : Q8_0, Q4_0, IQ4_NL (Q8_0 activations)
+//   FAM_Q8K : Q4_K, Q5_K, Q6_K, IQ4_XS, IQ3_S, IQ3_XXS (Q8_K activations)   FAM_Q80 : Q8_0, Q4_0, IQ4_NL (Q8_0 activations)
 enum { FAM_Q8K = 0, FAM_Q80 = 1 };
 __host__ __device__ constexpr bool fam_is_q8k(int fam) { return fam != FAM_Q80; }
 
@@ -48,7 +49,8 @@ __device__ __forceinline__ int dot16(const uint32_t w[4], const uint4 a) {
 
 // ------------------------------------------------------------------------------------------------
 // One in-flight payload chunk (16 bytes of packed quants) plus the side fields its lane needs.
-// chunk_load<T>() only issues global loads; Consume<T,N>::run() unpacks and accumulates.
+// chunk_load<T>() only issues global loads; Consume<T,N>::run() unpacks and accumulates (`grid`: the type's code book in LDS for
+// IQ3_S / IQ3_XXS, unused and null for every other type).
 // A row is cut into steps of 64 chunks; in step s lane l owns chunk c = 64*s + l.  `row` and `s` are
 // wave-uniform (SGPRs); everything derived from the lane id alone is loop-invariant.
 // ------------------------------------------------------------------------------------------------
@@ -56,8 +58,8 @@ struct Chunk {
     uint4    q;        // payload
     uint4    a;        // Q4_K/Q5_K: header (d, dmin, 12 scale bytes as 4 records)   Q6_K: qh bytes
     uint4    b;        // Q5_K: qh bytes
-    uint32_t sc;       // Q6_K: the two int8 sub-block scales (bytes 0 and 1)
-    uint32_t dh;       // f16 super-scale (Q6_K, Q8_0, Q4_0)
+    uint32_t sc;       // Q6_K: the two int8 sub-block scales (bytes 0 and 1)   IQ3_S: the scale byte of the sub-block pair
+    uint32_t dh;       // f16 super-scale (Q6_K, Q8_0, Q4_0, IQ3_S, IQ3_XXS)
 };
 
 template <int T> __device__ __forceinline__ void chunk_load(Chunk & ch, const uint8_t * row, int nb, int s, int lane);
@@ -99,7 +101,7 @@ template <int NCOLS> __device__ __forceinline__ void consume_q4k_q5k(const uint3
     }
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q4_K, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const uint32_t lo[4] = { ch.q.x & 0x0F0F0F0Fu, ch.q.y & 0x0F0F0F0Fu, ch.q.z & 0x0F0F0F0Fu, ch.q.w & 0x0F0F0F0Fu };
         const uint32_t hi[4] = { (ch.q.x >> 4) & 0x0F0F0F0Fu, (ch.q.y >> 4) & 0x0F0F0F0Fu, (ch.q.z >> 4) & 0x0F0F0F0Fu, (ch.q.w >> 4) & 0x0F0F0F0Fu };
         consume_q4k_q5k<NCOLS>(lo, hi, ch.a, s, lane, av, acc);
@@ -113,7 +115,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_Q5_K>(Chunk &
     ch.a = ldg16(row + 160 * nb + 128 * s + 16 * (lane >> 3));
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q5_K, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const int g = (lane >> 1) & 3;
         const uint32_t qw[4] = { ch.q.x, ch.q.y, ch.q.z, ch.q.w }, hw[4] = { ch.b.x, ch.b.y, ch.b.z, ch.b.w };
         uint32_t lo[4], hi[4];
@@ -137,7 +139,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_Q6_K>(Chunk &
     ch.dh = ldg<uint16_t>(row + 208 * nb + 16 * s + 2 * (lane >> 3));
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q6_K, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const int j = lane & 7, cc = (j >> 1) & 1;
         const int b = 8 * s + (lane >> 3);
         const uint32_t lw[4] = { ch.q.x, ch.q.y, ch.q.z, ch.q.w }, hw[4] = { ch.a.x, ch.a.y, ch.a.z, ch.a.w };
@@ -168,7 +170,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_Q8_0>(Chunk &
     ch.dh = ldg<uint16_t>(row + 32 * nb + 64 * s + 2 * (lane >> 1));
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q8_0, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const uint32_t w[4] = { ch.q.x, ch.q.y, ch.q.z, ch.q.w };
         const float dw = h2f(ch.dh);
         const int c = 64 * s + lane;
@@ -187,7 +189,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_Q4_0>(Chunk &
     ch.dh = ldg<uint16_t>(row + 16 * nb + 128 * s + 2 * lane);
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_Q4_0, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const uint32_t lo[4] = { ch.q.x & 0x0F0F0F0Fu, ch.q.y & 0x0F0F0F0Fu, ch.q.z & 0x0F0F0F0Fu, ch.q.w & 0x0F0F0F0Fu };
         const uint32_t hi[4] = { (ch.q.x >> 4) & 0x0F0F0F0Fu, (ch.q.y >> 4) & 0x0F0F0F0Fu, (ch.q.z >> 4) & 0x0F0F0F0Fu, (ch.q.w >> 4) & 0x0F0F0F0Fu };
         const float dw = h2f(ch.dh);
@@ -210,7 +212,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_IQ4_NL>(Chunk
     ch.dh = ldg<uint16_t>(row + 16 * nb + 128 * s + 2 * lane);
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_IQ4_NL, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const uint32_t qw[4] = { ch.q.x, ch.q.y, ch.q.z, ch.q.w };
         uint32_t lo[4], hi[4];
 #pragma unroll
@@ -232,7 +234,7 @@ template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_IQ4_XS>(Chunk
     ch.a.x = h.x; ch.a.y = h.y;
 }
 template <int NCOLS> struct Consume<MI355Q_TYPE_IQ4_XS, NCOLS> {
-    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc) {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
         const int j = lane & 7, b = 8 * s + (lane >> 3);
         const uint32_t qw[4] = { ch.q.x, ch.q.y, ch.q.z, ch.q.w };
         uint32_t lo[4], hi[4];
@@ -250,9 +252,97 @@ template <int NCOLS> struct Consume<MI355Q_TYPE_IQ4_XS, NCOLS> {
     }
 };
 
+// ---- the 3-bit code-book formats: a byte (IQ3_XXS) or 9 bits (IQ3_S: qs byte | one qh bit) index a code book of four unsigned magnitudes
+// (iq3xxs_grid 256 x u32, iq3s_grid 512 x u32; csrc/iq_tables.h), one sign bit per element.  The book of the type being streamed lives in
+// LDS (2 KiB / 1 KiB), copied once per workgroup.  A chunk is ONE 32-element sub-block: 8 payload bytes per lane, 512 contiguous bytes per wave
+// and step -- so a step is 8 blocks = 2048 elements like every other Q8_K-family type, lane roles are the K-quants', and a planar row
+// (K % 2048 == 0) never ends in a partial step.  (A 16-byte payload load would make the step 4096 elements: K = 14336 would end in half a step,
+// and a lane would hold 16 code book words at a time; the kernel is bound by the look-ups and the sign arithmetic, not by the width of the load.)
+__host__ __device__ constexpr bool type_is_iq3(int t) { return t == MI355Q_TYPE_IQ3_S || t == MI355Q_TYPE_IQ3_XXS; }
+__host__ __device__ constexpr int iq3_grid_words(int t) { return t == MI355Q_TYPE_IQ3_S ? 512 : t == MI355Q_TYPE_IQ3_XXS ? 256 : 0; }
+__host__ __device__ constexpr int iq3_grid_bytes(int t) { return 4 * iq3_grid_words(t); }    // LDS bytes of the type's book (0: the type has none)
+
+// word i of type T's book (i < iq3_grid_words(T)): a global load.  A workgroup of at least 512 threads moves a book with one word per thread:
+// fetch early, store to LDS once the loads in front of it have had their time, publish with the next barrier.
+template <int T> __device__ __forceinline__ uint32_t iq3_grid_word(int i) {
+    const uint8_t * g = T == MI355Q_TYPE_IQ3_S ? c_grid_iq3s[i] : c_grid_iq3xxs[i];
+    return (uint32_t) g[0] | (uint32_t) g[1] << 8 | (uint32_t) g[2] << 16 | (uint32_t) g[3] << 24;
+}
+
+__device__ __forceinline__ uint2 ldg8_nt(const void * p) {
+    const MI355Q_GLOBAL unsigned int * q = (const MI355Q_GLOBAL unsigned int *) p;
+    uint2 r;
+    r.x = __builtin_nontemporal_load(q);
+    r.y = __builtin_nontemporal_load(q + 1);
+    return r;
+}
+
+// sub-block sum against every column: gw[i] = code-book word of elements 4i .. 4i+3, signs = 32 sign bits in element order, ls = 2 * scale + 1
+template <int NCOLS> __device__ __forceinline__ void iq3_accumulate(const uint32_t gw[8], uint32_t signs, float d, int ls, int s, int lane,
+                                                                       const ActView * av, float * acc) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = iq3_signed4(gw[i], (signs >> (4 * i)) & 0xFu);
+    const int e = 2048 * s + 32 * lane, b = 8 * s + (lane >> 3);
+#pragma unroll
+    for (int n = 0; n < NCOLS; ++n) {
+        const int sumi = dot16(w, av[n].q16(e)) + dot16(w + 4, av[n].q16(e + 16));
+        acc[n] += (d * av[n].dK(b)) * (float) imul24(sumi, ls);      // CPU: exact integer sub-block sum times the odd scale, then d_x * d_y
+    }
+}
+
+// ---- IQ3_S planar: [qs 64*nb][signs 32*nb][qh 8*nb][scales 4*nb][d 2*nb]                                          ggml-common.h block_iq3_s
+template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_IQ3_S>(Chunk & ch, const uint8_t * row, int nb, int s, int lane) {
+    const uint2 q = ldg8_nt(row + 512 * s + 8 * lane);
+    ch.q.x = q.x; ch.q.y = q.y;
+    ch.a.x = ldg<uint32_t>(row + 64 * nb + 256 * s + 4 * lane);
+    ch.a.y = ldg<uint8_t>(row + 96 * nb + 64 * s + lane);
+    ch.sc  = ldg<uint8_t>(row + 104 * nb + 32 * s + (lane >> 1));
+    ch.dh  = ldg<uint16_t>(row + 108 * nb + 16 * s + 2 * (lane >> 3));
+}
+template <int NCOLS> struct Consume<MI355Q_TYPE_IQ3_S, NCOLS> {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
+        const uint32_t qh = ch.a.y;
+        uint32_t gw[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t qb = ((i < 4 ? ch.q.x : ch.q.y) >> (8 * (i & 3))) & 0xFFu;
+            gw[i] = grid[qb | (((qh >> i) & 1u) << 8)];            // (ggml-quants.c dequantize_row_iq3_s: qs[i] | bit i of qh as bit 8)
+        }
+        const int ls = 2 * (int) ((ch.sc >> (4 * (lane & 1))) & 0xFu) + 1;
+        iq3_accumulate<NCOLS>(gw, ch.a.x, h2f(ch.dh), ls, s, lane, av, acc);
+    }
+};
+
+// ---- IQ3_XXS planar: [qs 64*nb][scales_and_signs 32*nb][d 2*nb]                                                    ggml-common.h block_iq3_xxs
+// the sub-block's dword holds four 7-bit sign patterns (the eighth sign makes the number of minus signs even: ksigns_iq2xs[i] = i | parity(i) << 7)
+// and the 4-bit scale on top
+template <> __device__ __forceinline__ void chunk_load<MI355Q_TYPE_IQ3_XXS>(Chunk & ch, const uint8_t * row, int nb, int s, int lane) {
+    const uint2 q = ldg8_nt(row + 512 * s + 8 * lane);
+    ch.q.x = q.x; ch.q.y = q.y;
+    ch.a.x = ldg<uint32_t>(row + 64 * nb + 256 * s + 4 * lane);
+    ch.dh  = ldg<uint16_t>(row + 96 * nb + 16 * s + 2 * (lane >> 3));
+}
+template <int NCOLS> struct Consume<MI355Q_TYPE_IQ3_XXS, NCOLS> {
+    static __device__ __forceinline__ void run(const Chunk & ch, int s, int lane, const ActView * av, float * acc, const uint32_t * grid) {
+        const uint32_t aux = ch.a.x;
+        uint32_t gw[8], signs = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) gw[i] = grid[((i < 4 ? ch.q.x : ch.q.y) >> (8 * (i & 3))) & 0xFFu];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const uint32_t s7 = (aux >> (7 * l)) & 127u;
+            signs |= (s7 | (((uint32_t) __popc(s7) & 1u) << 7)) << (8 * l);
+        }
+        const int ls = 2 * (int) (aux >> 28) + 1;
+        // CPU: 0.25f * d * sum over the row; here 0.25 is folded into d (a power of two: the same bits unless d * 0.25 is subnormal in f32 -- f16 d >= 2^-24)
+        iq3_accumulate<NCOLS>(gw, signs, 0.25f * h2f(ch.dh), ls, s, lane, av, acc);
+    }
+};
+
 // chunks per row for a type
 __host__ __device__ __forceinline__ int row_chunks(int type, int k) {
-    return type == MI355Q_TYPE_Q8_0 ? k / 16 : k / 32;       // Q4_0 / IQ4_NL: one per 32-block; K-quants / IQ4_XS: 8 per 256-block
+    return type == MI355Q_TYPE_Q8_0 ? k / 16 : k / 32;       // Q4_0 / IQ4_NL: one per 32-block; K-quants / IQ4_XS / IQ3_S / IQ3_XXS: 8 per 256-block
 }
 
 // ------------------------------------------------------------------------------------------------

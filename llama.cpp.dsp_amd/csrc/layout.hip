@@ -9,9 +9,9 @@ namespace mi355q {
 struct PackDesc {
     int     nplanes;
     int     bsize;
-    int     src_off[4];
-    int     bytes[4];
-    int64_t start[5];      // byte offset of each plane inside a device row
+    int     src_off[5];
+    int     bytes[5];
+    int64_t start[6];      // byte offset of each plane inside a device row
     int64_t row_bytes;
     int     perm_plane;    // plane whose bytes are additionally permuted inside each block (-1: none)
     uint8_t perm[16];      // device byte i of that plane's per-block group = source byte perm[i]
@@ -29,7 +29,7 @@ k_repack(const uint16_t * __restrict__ src, uint16_t * __restrict__ dst, const P
         const int64_t o   = (i - row * words_per_row) * 2;           // byte offset inside the DEVICE row
         int p = 0;
 #pragma unroll
-        for (int t = 1; t < 4; ++t) if (t < d.nplanes && o >= d.start[t]) p = t;
+        for (int t = 1; t < 5; ++t) if (t < d.nplanes && o >= d.start[t]) p = t;
         const int64_t rel = o - d.start[p];
         const int64_t blk = rel / d.bytes[p];
         const int64_t off = rel - blk * d.bytes[p];
@@ -69,12 +69,12 @@ static bool make_desc(int type, int64_t k, PackDesc & d) {
     const int64_t nb = k / ti->blck;
     d.nplanes = ti->nplanes; d.bsize = ti->bsize; d.row_bytes = nb * ti->bsize;
     int64_t off = 0;
-    for (int p = 0; p < 4; ++p) {
+    for (int p = 0; p < 5; ++p) {
         d.src_off[p] = ti->planes[p].src_off; d.bytes[p] = ti->planes[p].bytes > 0 ? ti->planes[p].bytes : 1;
         d.start[p] = off;
         if (p < ti->nplanes) off += (int64_t) ti->planes[p].bytes * nb;
     }
-    d.start[4] = off;
+    d.start[5] = off;
     d.perm_plane = -1;
     for (int i = 0; i < 16; ++i) d.perm[i] = (uint8_t) i;
     d.kq_plane = type == MI355Q_TYPE_Q4_K ? 1 : (type == MI355Q_TYPE_Q5_K ? 2 : -1);   // (d, dmin, scales): the plane whose src_off is 0

@@ -16,7 +16,7 @@ namespace mi355q {
 constexpr int WAVE = 64;
 
 // ------------------------------------------------------------------------------------------------
-// Type table.  A canonical ggml block of `bsize` bytes is cut into up to 4 "planes"
+// Type table.  A canonical ggml block of `bsize` bytes is cut into up to 5 "planes"
 // (byte ranges).  In the PLANAR device layout a row of nb blocks stores plane 0 of all nb blocks,
 // then plane 1 of all blocks, ... so that every plane is a dense, 16-byte-aligned array a wave can
 // read with one global_load_dwordx4 per lane.  Row byte size and row stride equal the canonical ones.
@@ -29,36 +29,37 @@ struct TypeInfo {
     int   bsize;       // bytes per block
     int   act;         // activation format the CPU pairs with it (vec_dot_type, ggml-cpu.c:211-376)
     int   nplanes;
-    Plane planes[4];   // device order
+    Plane planes[5];   // device order
     int   fast;        // 1: a planar GEMV kernel exists
 };
 
 inline const TypeInfo * type_info(int type) {   // host only
     // planes: payload first (always 16-B aligned for a 16-B aligned row), small fields after
     static const TypeInfo tab[] = {
-        { MI355Q_TYPE_Q4_0,   32,  18, MI355Q_TYPE_Q8_0, 2, {{2, 16}, {0, 2}, {0, 0}, {0, 0}},            1 },
-        { MI355Q_TYPE_Q4_1,   32,  20, MI355Q_TYPE_Q8_1, 2, {{4, 16}, {0, 4}, {0, 0}, {0, 0}},            0 },
-        { MI355Q_TYPE_Q5_0,   32,  22, MI355Q_TYPE_Q8_0, 3, {{6, 16}, {2, 4}, {0, 2}, {0, 0}},            0 },
-        { MI355Q_TYPE_Q5_1,   32,  24, MI355Q_TYPE_Q8_1, 3, {{8, 16}, {4, 4}, {0, 4}, {0, 0}},            0 },
-        { MI355Q_TYPE_Q8_0,   32,  34, MI355Q_TYPE_Q8_0, 2, {{2, 32}, {0, 2}, {0, 0}, {0, 0}},            1 },
-        { MI355Q_TYPE_Q2_K,   256, 84, MI355Q_TYPE_Q8_K, 3, {{16, 64}, {0, 16}, {80, 4}, {0, 0}},         0 },
-        { MI355Q_TYPE_Q3_K,   256, 110, MI355Q_TYPE_Q8_K, 4, {{32, 64}, {0, 32}, {96, 12}, {108, 2}},     0 },
-        { MI355Q_TYPE_Q4_K,   256, 144, MI355Q_TYPE_Q8_K, 2, {{16, 128}, {0, 16}, {0, 0}, {0, 0}},        1 },
-        { MI355Q_TYPE_Q5_K,   256, 176, MI355Q_TYPE_Q8_K, 3, {{48, 128}, {16, 32}, {0, 16}, {0, 0}},      1 },
-        { MI355Q_TYPE_Q6_K,   256, 210, MI355Q_TYPE_Q8_K, 4, {{0, 128}, {128, 64}, {192, 16}, {208, 2}},  1 },
-        { MI355Q_TYPE_IQ4_NL, 32,  18, MI355Q_TYPE_Q8_0, 2, {{2, 16}, {0, 2}, {0, 0}, {0, 0}},            1 },
-        { MI355Q_TYPE_IQ4_XS, 256, 136, MI355Q_TYPE_Q8_K, 2, {{8, 128}, {0, 8}, {0, 0}, {0, 0}},          1 },
+        { MI355Q_TYPE_Q4_0,   32,  18, MI355Q_TYPE_Q8_0, 2, {{2, 16}, {0, 2}, {0, 0}, {0, 0}, {0, 0}},            1 },
+        { MI355Q_TYPE_Q4_1,   32,  20, MI355Q_TYPE_Q8_1, 2, {{4, 16}, {0, 4}, {0, 0}, {0, 0}, {0, 0}},            0 },
+        { MI355Q_TYPE_Q5_0,   32,  22, MI355Q_TYPE_Q8_0, 3, {{6, 16}, {2, 4}, {0, 2}, {0, 0}, {0, 0}},            0 },
+        { MI355Q_TYPE_Q5_1,   32,  24, MI355Q_TYPE_Q8_1, 3, {{8, 16}, {4, 4}, {0, 4}, {0, 0}, {0, 0}},            0 },
+        { MI355Q_TYPE_Q8_0,   32,  34, MI355Q_TYPE_Q8_0, 2, {{2, 32}, {0, 2}, {0, 0}, {0, 0}, {0, 0}},            1 },
+        { MI355Q_TYPE_Q2_K,   256, 84, MI355Q_TYPE_Q8_K, 3, {{16, 64}, {0, 16}, {80, 4}, {0, 0}, {0, 0}},         0 },
+        { MI355Q_TYPE_Q3_K,   256, 110, MI355Q_TYPE_Q8_K, 4, {{32, 64}, {0, 32}, {96, 12}, {108, 2}, {0, 0}},     0 },
+        { MI355Q_TYPE_Q4_K,   256, 144, MI355Q_TYPE_Q8_K, 2, {{16, 128}, {0, 16}, {0, 0}, {0, 0}, {0, 0}},        1 },
+        { MI355Q_TYPE_Q5_K,   256, 176, MI355Q_TYPE_Q8_K, 3, {{48, 128}, {16, 32}, {0, 16}, {0, 0}, {0, 0}},      1 },
+        { MI355Q_TYPE_Q6_K,   256, 210, MI355Q_TYPE_Q8_K, 4, {{0, 128}, {128, 64}, {192, 16}, {208, 2}, {0, 0}},  1 },
+        { MI355Q_TYPE_IQ4_NL, 32,  18, MI355Q_TYPE_Q8_0, 2, {{2, 16}, {0, 2}, {0, 0}, {0, 0}, {0, 0}},            1 },
+        { MI355Q_TYPE_IQ4_XS, 256, 136, MI355Q_TYPE_Q8_K, 2, {{8, 128}, {0, 8}, {0, 0}, {0, 0}, {0, 0}},          1 },
         // code-book formats: canonical layout, generic tier (code books: iq_tables.h)
-        { MI355Q_TYPE_IQ2_XXS, 256, 66,  MI355Q_TYPE_Q8_K, 1, {{0, 66}, {0, 0}, {0, 0}, {0, 0}},          0 },
-        { MI355Q_TYPE_IQ2_XS,  256, 74,  MI355Q_TYPE_Q8_K, 1, {{0, 74}, {0, 0}, {0, 0}, {0, 0}},          0 },
-        { MI355Q_TYPE_IQ2_S,   256, 82,  MI355Q_TYPE_Q8_K, 1, {{0, 82}, {0, 0}, {0, 0}, {0, 0}},          0 },
-        { MI355Q_TYPE_IQ3_XXS, 256, 98,  MI355Q_TYPE_Q8_K, 1, {{0, 98}, {0, 0}, {0, 0}, {0, 0}},          0 },
-        { MI355Q_TYPE_IQ3_S,   256, 110, MI355Q_TYPE_Q8_K, 1, {{0, 110}, {0, 0}, {0, 0}, {0, 0}},         0 },
-        { MI355Q_TYPE_IQ1_S,   256, 50,  MI355Q_TYPE_Q8_K, 1, {{0, 50}, {0, 0}, {0, 0}, {0, 0}},          0 },
-        { MI355Q_TYPE_IQ1_M,   256, 56,  MI355Q_TYPE_Q8_K, 1, {{0, 56}, {0, 0}, {0, 0}, {0, 0}},          0 },
+        { MI355Q_TYPE_IQ2_XXS, 256, 66,  MI355Q_TYPE_Q8_K, 1, {{0, 66}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},          0 },
+        { MI355Q_TYPE_IQ2_XS,  256, 74,  MI355Q_TYPE_Q8_K, 1, {{0, 74}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},          0 },
+        { MI355Q_TYPE_IQ2_S,   256, 82,  MI355Q_TYPE_Q8_K, 1, {{0, 82}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},          0 },
+        // ... except the 3-bit ones, which stream: qs | (IQ3_S: signs, qh, scales | IQ3_XXS: scales_and_signs) | d
+        { MI355Q_TYPE_IQ3_XXS, 256, 98,  MI355Q_TYPE_Q8_K, 3, {{2, 64}, {66, 32}, {0, 2}, {0, 0}, {0, 0}},        1 },
+        { MI355Q_TYPE_IQ3_S,   256, 110, MI355Q_TYPE_Q8_K, 5, {{2, 64}, {74, 32}, {66, 8}, {106, 4}, {0, 2}},     1 },
+        { MI355Q_TYPE_IQ1_S,   256, 50,  MI355Q_TYPE_Q8_K, 1, {{0, 50}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},          0 },
+        { MI355Q_TYPE_IQ1_M,   256, 56,  MI355Q_TYPE_Q8_K, 1, {{0, 56}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},          0 },
         // activation-only formats (never src0)
-        { MI355Q_TYPE_Q8_1,   32,  36, -1, 0, {{0, 0}, {0, 0}, {0, 0}, {0, 0}},                            0 },
-        { MI355Q_TYPE_Q8_K,   256, 292, -1, 0, {{0, 0}, {0, 0}, {0, 0}, {0, 0}},                           0 },
+        { MI355Q_TYPE_Q8_1,   32,  36, -1, 0, {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},                            0 },
+        { MI355Q_TYPE_Q8_K,   256, 292, -1, 0, {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}},                           0 },
     };
     for (unsigned i = 0; i < sizeof(tab) / sizeof(tab[0]); ++i)
         if (tab[i].type == type) return &tab[i];
@@ -110,6 +111,15 @@ __device__ __forceinline__ uint32_t iq4_lut4(uint32_t nib) {
     const uint32_t b = __builtin_amdgcn_perm(0x71594535u, 0x26190D01u, sel);      // entries 8..15
     const uint32_t m = ((nib >> 3) & 0x01010101u) * 0xFFu;
     return (a & ~m) | (b & m);
+}
+
+// IQ3_S / IQ3_XXS: Four code-book magnitudes (bytes of g, each 1 .. 62: never zero, top bit clear) with the sign bits nib[3:0] applied, as int8.  The four bits are
+// spread to the low bit of each byte by one 24-bit multiply (bit i lands on 8 i; the stray copies fall on other bit positions and are masked off),
+// m = m1 * 255 is the byte mask, and (g ^ m) + m1 negates the chosen bytes in two's complement -- no carry leaves a byte because g != 0.
+__device__ __forceinline__ uint32_t iq3_signed4(uint32_t g, uint32_t nib) {
+    const uint32_t m1 = (uint32_t) __mul24((int) nib, 0x204081) & 0x01010101u;
+    const uint32_t m  = (m1 << 8) - m1;
+    return (g ^ m) + m1;
 }
 
 __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & 63); }

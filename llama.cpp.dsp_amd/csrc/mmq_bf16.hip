@@ -18,6 +18,7 @@
 // by the CPU's own Q8_K activation quantization; measured NMSE ~1e-5, bound 5e-4 (tests/test-backend-ops.cpp:1990).
 // Bound: MFMA (2*M*N*K flop); HBM traffic = packed W once per 128-token column tile + bf16 activations.
 #include "mi355q_common.h"
+#include "iq_tables.h"
 
 namespace mi355q {
 
@@ -241,6 +242,51 @@ template <> struct W32<MI355Q_TYPE_IQ4_XS> {        // planar [qs 128*nb][hdr 8*
     }
 };
 
+// ---- IQ3_S / IQ3_XXS: 32 k = one sub-block sb of the row; code books read from device memory (3 KiB, cache resident), signs applied in the
+// integer domain (iq3_signed4), one f32 multiply per weight by the sub-block's scale as dequantize_row_iq3_s / _xxs form it (ggml-quants.c:2284-2357)
+__device__ __forceinline__ uint32_t mmq_grid_word(const uint8_t * g) { return (uint32_t) g[0] | (uint32_t) g[1] << 8 | (uint32_t) g[2] << 16 | (uint32_t) g[3] << 24; }
+template <> struct W32<MI355Q_TYPE_IQ3_S> {         // planar [qs 64*nb][signs 32*nb][qh 8*nb][scales 4*nb][d 2*nb]
+    W32_DEQUANT16
+    uint2 q; uint32_t sg, qh, sc, dh; int odd;
+    __device__ __forceinline__ void load(const uint8_t * row, int nb, int ks, int sub) {
+        const int64_t sb = 2 * (int64_t) ks + sub;
+        q  = ldg<uint2>(row + 8 * sb);
+        sg = ldg<uint32_t>(row + 64 * (int64_t) nb + 4 * sb);
+        qh = ldg<uint8_t>(row + 96 * (int64_t) nb + sb);
+        sc = ldg<uint8_t>(row + 104 * (int64_t) nb + (sb >> 1));
+        dh = ldg<uint16_t>(row + 108 * (int64_t) nb + 2 * (sb >> 3));
+        odd = sub;
+    }
+    __device__ __forceinline__ void dequant(uint32_t * out) const {
+        const float db = h2f(dh) * (float) (1 + 2 * (int) ((sc >> (4 * odd)) & 0xFu));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t qb = ((i < 4 ? q.x : q.y) >> (8 * (i & 3))) & 0xFFu;
+            const uint32_t g = mmq_grid_word(c_grid_iq3s[qb | (((qh >> i) & 1u) << 8)]);
+            sbytes4_to_bf16(iq3_signed4(g, (sg >> (4 * i)) & 0xFu), db, out[2 * i], out[2 * i + 1]);
+        }
+    }
+};
+template <> struct W32<MI355Q_TYPE_IQ3_XXS> {       // planar [qs 64*nb][scales_and_signs 32*nb][d 2*nb]
+    W32_DEQUANT16
+    uint2 q; uint32_t aux, dh;
+    __device__ __forceinline__ void load(const uint8_t * row, int nb, int ks, int sub) {
+        const int64_t sb = 2 * (int64_t) ks + sub;
+        q   = ldg<uint2>(row + 8 * sb);
+        aux = ldg<uint32_t>(row + 64 * (int64_t) nb + 4 * sb);
+        dh  = ldg<uint16_t>(row + 96 * (int64_t) nb + 2 * (sb >> 3));
+    }
+    __device__ __forceinline__ void dequant(uint32_t * out) const {
+        const float db = h2f(dh) * (0.5f + (float) (aux >> 28)) * 0.5f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t g = mmq_grid_word(c_grid_iq3xxs[((i < 4 ? q.x : q.y) >> (8 * (i & 3))) & 0xFFu]);
+            const uint32_t s7 = (aux >> (7 * (i >> 1))) & 127u, s8 = s7 | (((uint32_t) __popc(s7) & 1u) << 7);     // (ksigns_iq2xs: the eighth sign makes the count even)
+            sbytes4_to_bf16(iq3_signed4(g, (s8 >> (4 * (i & 1))) & 0xFu), db, out[2 * i], out[2 * i + 1]);
+        }
+    }
+};
+
 // ---- the kernel ---------------------------------------------------------------------------------
 // Tile BM x BN x 128; 256 threads = 2 x 2 waves, each a (BM/2) x (BN/2) output tile of 16x16x32 MFMAs.  Thread jobs per
 // K-step: BM*4/256 dequant units (row, 32-k quarter) and BN*4/256 activation quarters (64 B).  Shapes that would leave
@@ -384,6 +430,7 @@ void launch_mmq_reduce(const float * part, int n_split, int64_t split_stride, fl
 bool mmq_supported(int type, int64_t k) {
     switch (type) {
     case MI355Q_TYPE_Q4_K: case MI355Q_TYPE_Q5_K: case MI355Q_TYPE_Q6_K: case MI355Q_TYPE_IQ4_XS: return k % 256 == 0;
+    case MI355Q_TYPE_IQ3_S: case MI355Q_TYPE_IQ3_XXS: return k % 2048 == 0;      // (planar exactly at these K)
     case MI355Q_TYPE_Q8_0: case MI355Q_TYPE_Q4_0: case MI355Q_TYPE_IQ4_NL: return k % 128 == 0;
     default: return false;
     }
@@ -457,6 +504,7 @@ int launch_mmq_bf16(int type, const void * w, int64_t w_stride, const float * x,
     switch (type) {
         MI355Q_MMQ_CASE(MI355Q_TYPE_Q4_K) MI355Q_MMQ_CASE(MI355Q_TYPE_Q5_K) MI355Q_MMQ_CASE(MI355Q_TYPE_Q6_K)
         MI355Q_MMQ_CASE(MI355Q_TYPE_Q8_0) MI355Q_MMQ_CASE(MI355Q_TYPE_Q4_0) MI355Q_MMQ_CASE(MI355Q_TYPE_IQ4_NL) MI355Q_MMQ_CASE(MI355Q_TYPE_IQ4_XS)
+        MI355Q_MMQ_CASE(MI355Q_TYPE_IQ3_S) MI355Q_MMQ_CASE(MI355Q_TYPE_IQ3_XXS)
     default: return MI355Q_ERR_UNSUPPORTED;
     }
 #undef MI355Q_MMQ_CASE

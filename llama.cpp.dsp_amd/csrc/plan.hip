@@ -38,6 +38,8 @@ namespace mi355q {
 
 constexpr int PLAN_D_MAX = 8;                     // ring depth (1-KiB steps in flight per wave)
 __host__ __device__ constexpr int plan_depth(int type) {   // Q5_K / Q6_K slots carry qh too (1.5 KiB per step): 6 steps are the bytes of 8 Q4_K steps
+    // IQ3_S / IQ3_XXS: a step of a wave is 880 / 784 bytes (512 of code-book indices + signs, qh, scales, d) in 6 / 4 registers per lane -- less
+    // than Q4_K's 1152 bytes in 8, so the full depth, which is still fewer bytes in flight than Q4_K's
     return (type == MI355Q_TYPE_Q5_K || type == MI355Q_TYPE_Q6_K) ? 6 : PLAN_D_MAX;
 }
 enum { PLAN_F_NEW_X = 2, PLAN_F_PLAIN_Y = 4, PLAN_F_SUM = 8, PLAN_F_SUM_PLAIN = 16, PLAN_F_PAIRED = 32, PLAN_F_DIRECT = 64, PLAN_F_ATTN_LDS = 128, PLAN_F_ATTN_Q = 256 };
@@ -97,7 +99,13 @@ constexpr unsigned SET_80   = tbit(MI355Q_TYPE_Q8_0) | tbit(MI355Q_TYPE_Q4_0);
 constexpr unsigned SET_ALL  = SET_K456 | SET_80;
 // IQ4_XS / IQ4_NL models (llama-quant.cpp: IQ4_XS or IQ4_NL for most tensors, Q5_K / Q6_K for attn_v, some ffn_down and the output matrix)
 constexpr unsigned SET_IQ4  = tbit(MI355Q_TYPE_IQ4_XS) | tbit(MI355Q_TYPE_IQ4_NL) | tbit(MI355Q_TYPE_Q5_K) | tbit(MI355Q_TYPE_Q6_K);
-constexpr unsigned SET_ANY  = SET_ALL | SET_IQ4;
+// IQ3_XS / IQ3_S / IQ3_M / IQ3_XXS models (llama-quant.cpp: IQ3_S or IQ3_XXS for most tensors, Q4_K / Q5_K / Q6_K for attn_v, some ffn_down, the output matrix).
+// The code books live in LDS for the whole launch, in the last IQ3_BOOKS_BYTES of the image area: [iq3s_grid 2 KiB][iq3xxs_grid 1 KiB].
+constexpr unsigned SET_IQ3B = tbit(MI355Q_TYPE_IQ3_S) | tbit(MI355Q_TYPE_IQ3_XXS);
+constexpr unsigned SET_IQ3  = SET_IQ3B | SET_K456;
+constexpr int IQ3_BOOKS_BYTES = iq3_grid_bytes(MI355Q_TYPE_IQ3_S) + iq3_grid_bytes(MI355Q_TYPE_IQ3_XXS);
+__host__ __device__ constexpr int iq3_book_offset(int t) { return t == MI355Q_TYPE_IQ3_S ? 0 : iq3_grid_bytes(MI355Q_TYPE_IQ3_S); }
+constexpr unsigned SET_ANY  = SET_ALL | SET_IQ4 | SET_IQ3;
 // a GEMV stage whose rows end in a partial step (row_chunks % 64 != 0) needs the row loop with the per-lane tail test; every other plan (every
 // Llama K: 4096, 8192, 14336, 28672) gets the kernel without it.  Not a weight type: the high bit of the set.
 constexpr unsigned SET_TAIL = 1u << 31;
@@ -230,7 +238,7 @@ __device__ __forceinline__ float unary_f(int uop, float x);
 // consume this wave's rows of the stage; slot d holds item d, d+D, ... ; refills keep D items in flight
 template <int T, int D, bool NOTAIL>
 __device__ __forceinline__ void plan_run(Chunk (&ring)[D], PlanCursor & ld, const StageW & st, const StageGeom & g, int r_lo, int wave, int lane,
-                                         const ActView * av, unsigned tag, bool plain, int pair_p0, int pair_unary) {
+                                         const ActView * av, const uint32_t * grid, unsigned tag, bool plain, int pair_p0, int pair_unary) {
     // the consumers' lane-invariant state (LDS offsets, shifts) is derived from an opaque copy of the lane id HERE, so
     // that it cannot be computed (and kept live, and spilled) before the prologue
     int lane_c = lane; asm volatile("" : "+v"(lane_c));
@@ -241,7 +249,7 @@ __device__ __forceinline__ void plan_run(Chunk (&ring)[D], PlanCursor & ld, cons
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (cs_gr < g.r_hi) {                             // wave-uniform
-                if (NOTAIL || 64 * cs_s + lane_c < g.nchunks) Consume<T, 1>::run(ring[d], cs_s, lane_c, av, acc);
+                if (NOTAIL || 64 * cs_s + lane_c < g.nchunks) Consume<T, 1>::run(ring[d], cs_s, lane_c, av, acc, grid);
                 if (++cs_s == g.steps) {                      // row finished: reduce, publish (one granule), next row
                     const float t = wave_sum(acc[0]);
                     if (st.paired) {                           // (wave-uniform)
@@ -584,9 +592,10 @@ static __device__ __forceinline__ bool plan_stage(StageC st, const StageCtx & c)
     PLAN_STAMP(3);
     ActView av[1];
     av[0].base = c.lds; av[0].k = k;
+    const uint32_t * const grid = type_is_iq3(T) ? (const uint32_t *) (c.lds + c.image - IQ3_BOOKS_BYTES + iq3_book_offset(T)) : nullptr;   // (see SET_IQ3)
     // (a PAIRED stage publishes unary(row of matrix 0) * (row of matrix 1) per pair from the wave that streamed both: the output unary is kept in
     // the high byte of x_unary)
-    plan_run<T, PLAN_D, NOTAIL>(ring, ld, sw, g, r_lo, wave, lane, av, c.epoch + st->tag_off, (flags & PLAN_F_PLAIN_Y) != 0, pair_p0, st->x_unary >> 8);
+    plan_run<T, PLAN_D, NOTAIL>(ring, ld, sw, g, r_lo, wave, lane, av, grid, c.epoch + st->tag_off, (flags & PLAN_F_PLAIN_Y) != 0, pair_p0, st->x_unary >> 8);
     PLAN_STAMP(4);
     return true;
 }
@@ -1573,6 +1582,14 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
     c.pre_lds = (unsigned) (size_t) (lds + lds_image_bytes + 64 + 8 * GEMV_WAVES);
     c.sync = sync; c.timeout = timeout_ticks; c.grid = gridDim.x; c.even = even; c.epoch = epoch; c.image = lds_image_bytes;
     if (threadIdx.x == 0) c.ctl[CTL_OK] = 1;
+    if constexpr ((SET & SET_IQ3B) != 0) {                    // the code books, once per launch: one word per thread (the host put their 3 KiB at the end of the image area)
+        uint32_t * books = (uint32_t *) (lds + lds_image_bytes - IQ3_BOOKS_BYTES);
+        constexpr int NS = iq3_grid_words(MI355Q_TYPE_IQ3_S), NX = iq3_grid_words(MI355Q_TYPE_IQ3_XXS);
+        static_assert(NS + NX <= GEMV_THREADS, "one code-book word per thread");
+        const int tid = (int) threadIdx.x;
+        if (tid < NS) books[tid] = iq3_grid_word<MI355Q_TYPE_IQ3_S>(tid);
+        else if (tid < NS + NX) books[tid] = iq3_grid_word<MI355Q_TYPE_IQ3_XXS>(tid - NS);
+    }
     plan_lds_barrier();
 
 #pragma unroll 1
@@ -1606,6 +1623,8 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
             case MI355Q_TYPE_Q4_0: if constexpr ((SET & tbit(MI355Q_TYPE_Q4_0)) != 0) ok = plan_stage<MI355Q_TYPE_Q4_0, NOTAIL>(st, c); break;
             case MI355Q_TYPE_IQ4_NL: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_NL)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_NL, NOTAIL>(st, c); break;
             case MI355Q_TYPE_IQ4_XS: if constexpr ((SET & tbit(MI355Q_TYPE_IQ4_XS)) != 0) ok = plan_stage<MI355Q_TYPE_IQ4_XS, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_IQ3_S: if constexpr ((SET & tbit(MI355Q_TYPE_IQ3_S)) != 0) ok = plan_stage<MI355Q_TYPE_IQ3_S, NOTAIL>(st, c); break;
+            case MI355Q_TYPE_IQ3_XXS: if constexpr ((SET & tbit(MI355Q_TYPE_IQ3_XXS)) != 0) ok = plan_stage<MI355Q_TYPE_IQ3_XXS, NOTAIL>(st, c); break;
             default: break;
             }
         } else if (kind == PLAN_K_ATTN) {
@@ -1678,7 +1697,8 @@ template <unsigned TAIL> static const void * plan_kernel_t(unsigned set) {
     if ((set & ~SET_80) == 0)   return (const void *) k_plan<SET_80 | TAIL>;
     if ((set & ~SET_ALL) == 0)  return (const void *) k_plan<SET_ALL | TAIL>;
     if ((set & ~SET_IQ4) == 0)  return (const void *) k_plan<SET_IQ4 | TAIL>;
-    return nullptr;                                            // (a mix of the IQ4 types with Q4_K / Q8_0 / Q4_0: no instantiation)
+    if ((set & ~SET_IQ3) == 0)  return (const void *) k_plan<SET_IQ3 | TAIL>;
+    return nullptr;                                            // (a mix of the IQ4 types with Q4_K / Q8_0 / Q4_0, of the IQ3 types with anything but the K-quants: no instantiation)
 }
 static const void * plan_kernel(unsigned set) {
     return (set & SET_TAIL) ? plan_kernel_t<SET_TAIL>(set & ~SET_TAIL) : plan_kernel_t<0>(set);
@@ -1917,6 +1937,7 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
         }
     }
     if (set == 0) { mi355q_set_error("plan_create: a plan needs at least one GEMV stage"); return MI355Q_ERR_UNSUPPORTED; }
+    if (set & SET_IQ3B) lds_max += IQ3_BOOKS_BYTES;            // the code books behind the largest activation image (k_plan copies them in; plan_stage reads them at image - IQ3_BOOKS_BYTES)
     {   // the stage that consumes an attention output (wo) runs on the workgroups that did NOT run the attention (MI355Q_PLAN_WO_SKIP=0: on all)
         const bool no_skip = getenv("MI355Q_PLAN_WO_SKIP") && atoi(getenv("MI355Q_PLAN_WO_SKIP")) == 0;
         for (size_t si = 1; si < v.size() && !no_skip; ++si) {

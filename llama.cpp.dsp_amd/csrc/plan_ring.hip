@@ -802,7 +802,7 @@ static __device__ __forceinline__ bool plan_stage(StageC st, const Ctx & c, Prog
                 else        chunk_lds<T, true>(nxt, rv, g.nb, s + 1, lane);
             }
             float acc[1] = { 0.0f };
-            if (64 * s + lane < g.nchunks) Consume<T, 1>::run(cur, s, lane, av, acc);
+            if (64 * s + lane < g.nchunks) Consume<T, 1>::run(cur, s, lane, av, acc, nullptr);
             terms[(cslot * NS + s) * 64 + lane] = acc[0];
             cur = nxt;
         }
@@ -871,7 +871,7 @@ static __device__ __forceinline__ bool plan_stage(StageC st, const Ctx & c, Prog
 #pragma unroll 1
             for (int s = 0; s < NS; ++s) {
                 if (s + 1 < NS && 64 * (s + 1) + lane < g.nchunks) { if (!wraps) chunk_lds<T, false>(nxt, rv, g.nb, s + 1, lane); else chunk_lds<T, true>(nxt, rv, g.nb, s + 1, lane); }
-                if (64 * s + lane < g.nchunks) Consume<T, 1>::run(cur, s, lane, av, acc);
+                if (64 * s + lane < g.nchunks) Consume<T, 1>::run(cur, s, lane, av, acc, nullptr);
                 cur = nxt;
             }
             return wave_sum(acc[0]);
@@ -1486,6 +1486,7 @@ int mi355q_ring_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             if (done[i]) continue;
             const int type = in.mats[i].type;
             const int fam = gemv_fast_family(type);
+            if (type_is_iq3(type)) { mi355q_set_error("plan_create: the ring engine does not stream IQ3_S / IQ3_XXS (no code book in its LDS layout); use the regs engine"); return MI355Q_ERR_UNSUPPORTED; }
             if (fam < 0 || !(tbit(type) & SET_ANY) || !mi355q_weights_are_planar(type, in.k)) { mi355q_set_error("plan_create: weight type / k has no planar streaming kernel in the plan"); return MI355Q_ERR_UNSUPPORTED; }
             const int64_t row_bytes = mi355q_row_size(type, in.k);
             PlanStage p = {};
