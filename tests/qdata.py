@@ -58,3 +58,125 @@ def _ref():
     if _REF is None:
         _REF = oracle.Reference("scalar")
     return _REF
+
+
+# ------------------------------------------------------------------------------------------------
+# exact data: inputs whose product is an exact f32 number, whatever the order of the additions
+# ------------------------------------------------------------------------------------------------
+# Every dequantized weight of exact_blocks is  EXACT_UNIT[t] * integer  with |integer| < 256 (so it is a bf16 number), every activation of
+# exact_acts an integer of magnitude <= 127 (a bf16 number too).  A product is then UNIT * integer, and as long as  sum |w| |x| < 2^24 UNITs
+# every partial sum of every summation order is an exact f32: a kernel's answer can be held to equality with the float64 product.
+# The payload (quants, signs, grid indices) stays random over all its values; only the scale fields are restricted.  Limits, from the
+# dequantization formulas (oracle/orc_core.c, oracle/orc_iq.c; layouts oracle/orc_formats.h), largest |integer| in brackets:
+#   Q4_0 d (q-8), d in {1,2,4} D [32]       Q5_0 d (q-16), d in {1,2,4} D [64]     Q8_0 d q, d = D [128]
+#   Q4_1 d q + m, d = D, m in -{4,8,16} D [16]                                       Q5_1 d q + m, m in -{8,16,32} D [32]
+#   Q2_K d sc q - dmin m: 4-bit fields, any value [45]                                Q3_K d (sc-32)(q-4|q): any 6-bit sc [128]
+#   Q4_K d sc q - dmin m: sc, m <= 15 [225]    Q5_K sc <= 8, m <= 15 [248]          Q6_K d sc (q-32): |sc| <= 7 [224]
+#   IQ4_NL d kv, d in {+-1,+-2} D [254]        IQ4_XS d (ls-32) kv: ls-32 in {+-1,+-2} [254]
+#   IQ3_S d (1+2s) g, g <= 15: s <= 7 [225]    IQ3_XXS d/4 (1+2s) g, g <= 62: s <= 1 [186]
+#   IQ2_XXS / IQ2_XS / IQ2_S d/8 (1+2s) g, g <= 43: s <= 2 [215]
+#   IQ1_S / IQ1_M d/8 (1+2s) (8g +- 1), |g| <= 1, 3-bit s: any value [135]
+_EXACT_D = 2.0 ** -6             # D: the one power of two behind every f16 scale field
+EXACT_UNIT = {t: _EXACT_D for t in _F16_FIELDS}
+EXACT_UNIT.update({oracle.IQ3_XXS: _EXACT_D / 4, oracle.IQ2_XXS: _EXACT_D / 8, oracle.IQ2_XS: _EXACT_D / 8, oracle.IQ2_S: _EXACT_D / 8,
+                   oracle.IQ1_S: _EXACT_D / 8, oracle.IQ1_M: _EXACT_D / 8})
+
+
+def _f16_bytes(v: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(v.astype(np.float16)).view(np.uint8).reshape(v.shape + (2,))
+
+
+def _pack_k4_scales(sc: np.ndarray, mn: np.ndarray) -> np.ndarray:
+    """8 six-bit (scale, min) pairs -> the 12 scale bytes of a Q4_K / Q5_K block (the inverse of get_scale_min_k4)."""
+    out = np.zeros(sc.shape[:-1] + (12,), np.uint8)
+    out[..., 0:4] = (sc[..., 0:4] & 63) | ((sc[..., 4:8] >> 4) << 6)
+    out[..., 4:8] = (mn[..., 0:4] & 63) | ((mn[..., 4:8] >> 4) << 6)
+    out[..., 8:12] = (sc[..., 4:8] & 15) | ((mn[..., 4:8] & 15) << 4)
+    return out
+
+
+def exact_blocks(t: int, nrows: int, k: int, rng: np.random.Generator) -> np.ndarray:
+    """Packed rows of type t with random payloads whose every dequantized weight is EXACT_UNIT[t] * integer, |integer| < 256."""
+    bs, fields = _F16_FIELDS[t]
+    nb = k // BLCK[t]
+    w = rng.integers(0, 256, (nrows, nb, bs), dtype=np.uint8)
+    D = _EXACT_D
+    shp = (nrows, nb)
+    u8 = lambda lo, hi, *tail: rng.integers(lo, hi, shp + tail).astype(np.uint8)
+    d = np.full(shp, D)
+    if t in (oracle.Q4_0, oracle.Q5_0):
+        d = D * rng.choice([1.0, 2.0, 4.0], shp)
+    elif t == oracle.IQ4_NL:
+        d = D * rng.choice([-2.0, -1.0, 1.0, 2.0], shp)
+    for off in fields:
+        w[:, :, off:off + 2] = _f16_bytes(d)
+    if t in (oracle.Q4_1, oracle.Q5_1):                       # m: a negative multiple of d, so both signs occur
+        w[:, :, 2:4] = _f16_bytes(-D * rng.choice([4.0, 8.0, 16.0] if t == oracle.Q4_1 else [8.0, 16.0, 32.0], shp))
+    elif t in (oracle.Q4_K, oracle.Q5_K):
+        sc = rng.integers(0, 16 if t == oracle.Q4_K else 9, shp + (8,)).astype(np.uint8)
+        w[:, :, 4:16] = _pack_k4_scales(sc, u8(0, 16, 8))
+    elif t == oracle.Q6_K:
+        w[:, :, 192:208] = rng.integers(-7, 8, shp + (16,)).astype(np.int8).view(np.uint8)
+    elif t == oracle.IQ4_XS:
+        ls = rng.choice(np.array([30, 31, 33, 34], np.uint16), shp + (8,))
+        sh = np.zeros(shp, np.uint16)
+        for ib in range(8):
+            sh |= (ls[..., ib] >> 4) << (2 * ib)
+        w[:, :, 2:4] = np.ascontiguousarray(sh).view(np.uint8).reshape(shp + (2,))
+        w[:, :, 4:8] = ((ls[..., 0::2] & 15) | ((ls[..., 1::2] & 15) << 4)).astype(np.uint8)
+    elif t == oracle.IQ3_S:                                   # scales[4] at 106: two 4-bit scales per byte
+        w[:, :, 106:110] = u8(0, 8, 4) | (u8(0, 8, 4) << 4)
+    elif t == oracle.IQ3_XXS:                                 # top nibble of each of the 8 scales_and_signs words (2 + 64 + 4 ib + 3)
+        top = w[:, :, 69:98:4]
+        w[:, :, 69:98:4] = (top & 0x0F) | (u8(0, 2, 8) << 4)
+    elif t == oracle.IQ2_XXS:                                 # top nibble of the second word of each 8-byte group (2 + 8 ib + 7)
+        top = w[:, :, 9:66:8]
+        w[:, :, 9:66:8] = (top & 0x0F) | (u8(0, 3, 8) << 4)
+    elif t in (oracle.IQ2_XS, oracle.IQ2_S):                  # scales[8] behind the payload: two 4-bit scales per byte
+        off = 66 if t == oracle.IQ2_XS else 74
+        w[:, :, off:off + 8] = u8(0, 3, 8) | (u8(0, 3, 8) << 4)
+    elif t == oracle.IQ1_M:                                   # the f16 super-scale is scattered over the top nibbles of scales[4] (u16 at 48..55)
+        h = int(np.float16(D).view(np.uint16))
+        for i in range(4):
+            w[:, :, 49 + 2 * i] = (w[:, :, 49 + 2 * i] & 0x0f) | (((h >> (4 * i)) & 0xf) << 4)
+    return w.reshape(nrows, nb * bs)
+
+
+def exact_acts(n: int, k: int, rng: np.random.Generator, kind: str = "bf16") -> np.ndarray:
+    """Integer activations in [-16, 16] as f32 [n, k].  kind "q8_0" / "q8_k" adds the one element per 32- / 256-block that makes the CPU's
+    activation quantizer the identity (amax = 127: d = 1, quants == x), placed as tests/test_gpu_parity.py places it."""
+    x = rng.integers(-16, 17, (n, k)).astype(np.float32)
+    if kind == "q8_0":
+        x.reshape(n, k // 32, 32)[:, :, 0] = 127.0
+    elif kind == "q8_k":
+        x.reshape(n, k // 256, 256)[:, :, 3] = -127.0
+    else:
+        assert kind == "bf16", kind
+    return x
+
+
+def exact_product(orc, t: int, w: np.ndarray, x: np.ndarray, K: int, dq: np.ndarray | None = None) -> np.ndarray:
+    """The float64 product of the dequantized weights and the activations, as f32 [n, nrows]: the only reference of the exact tests.
+    (dq: orc.dequantize(t, w, K) where the caller already has it.)"""
+    dq = orc.dequantize(t, w, K) if dq is None else dq
+    return (x.astype(np.float64) @ dq.astype(np.float64).T).astype(np.float32)
+
+
+def exact_sum_bound(orc, t: int, w: np.ndarray, x: np.ndarray, K: int, dq: np.ndarray | None = None) -> float:
+    """An upper bound, in EXACT_UNITs, of sum |w| |x| over every (row, token) of the product and of the partial terms a kernel may form on the
+    way: max over rows of sum_k (|w[k]| + 2 mins) * max over tokens |x[k]|, where `mins` (15 for Q4_K / Q5_K / Q2_K, else 0) covers the
+    integer tiers, which add d sc sum(q x) and dmin m sum(x) separately.  Below 2^24 every partial sum is an exact f32."""
+    wi = np.abs((orc.dequantize(t, w, K) if dq is None else dq).astype(np.float64)) / EXACT_UNIT[t]
+    mins = 15.0 if t in (oracle.Q4_K, oracle.Q5_K, oracle.Q2_K) else 0.0
+    return float(((wi + 2.0 * mins) @ np.abs(x).max(axis=0).astype(np.float64)).max())
+
+
+# K values of tests/test_gpu_mmq_forms.py (tests/test_exact_data_cpu.py proves the 2^24 precondition for them without a GPU):
+# the type's smallest planar K, then the K of the split-K forms (4 pieces, 8 pieces; uneven step counts where the type's planar K allow them)
+_Q = oracle
+EXACT_FORM_KS = {
+    _Q.Q4_K: (256, 4096, 4352, 8192, 8448), _Q.Q5_K: (256, 4096, 4352, 8448), _Q.Q4_0: (256, 4096, 4352, 8448), _Q.IQ4_NL: (256, 4096, 4352, 8448),
+    _Q.Q8_0: (256, 4096, 4352, 8448), _Q.IQ4_XS: (512, 4096, 8704), _Q.Q6_K: (2048, 4096, 8192), _Q.IQ3_S: (2048, 4096, 8192),
+    _Q.IQ3_XXS: (2048, 4096, 8192),
+}
+EXACT_CANONICAL_K = {t: (384 if BLCK[t] == 32 else 512) for t in _F16_FIELDS}      # rows stay canonical at these K for every type that has a planar form
