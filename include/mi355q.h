@@ -83,7 +83,8 @@ extern "C" {
 /* flags for mi355q_mul_mat* / mi355q_quantize_act */
 #define MI355Q_FLAG_ROUND_AWAY   0x0  /* Q8_0/Q8_1 activations: q = roundf(x/d)   (quantize_row_q8_0_ref; default) */
 #define MI355Q_FLAG_ROUND_EVEN   0x1  /*                        q = rint(x/d)     (what the AVX2 / NEON CPU paths do) */
-#define MI355Q_FLAG_FORCE_GENERIC 0x2 /* debugging: use the generic (canonical-layout-style) kernel tier            */
+#define MI355Q_FLAG_FORCE_GENERIC 0x2 /* canonical rows only: keep them on the per-column tier (k_gemv_generic) for N > 8, off the
+                                         batched canonical tier.  Planar rows ignore it: no flag sends them to the generic kernel */
 #define MI355Q_FLAG_FORCE_GEMV   0x4  /* use the GEMV tier even for large N                                         */
 #define MI355Q_FLAG_FORCE_MMQ    0x8  /* use the tiled MFMA tier even for small N                                   */
 

@@ -332,7 +332,8 @@ static int launch_gemv_fast_typed(const mi355q_mat * mats, int n_mats, const flo
     if (rows == 0) return MI355Q_OK;
     if (rows > 0x7FFFFFF0) return MI355Q_ERR_UNSUPPORTED;
     a.x = x; a.x_stride = x_stride; a.total_rows = rows; a.n_mats = n_mats; a.k = (int) k;
-    a.x_vec = (((uintptr_t) x | (uintptr_t) x_stride) & 15) == 0 ? 1 : 0;
+    // (MUL_MAT_ID: a pair's activations start at x + t * x_stride2 -- the token stride has to keep the 16-byte alignment too)
+    a.x_vec = (((uintptr_t) x | (uintptr_t) x_stride | (uintptr_t) (moe ? moe->x_stride2 : 0)) & 15) == 0 ? 1 : 0;
     int pairs = 1;
     if (moe) {
         if (n_mats != 1 || ncols != 1) return MI355Q_ERR_UNSUPPORTED;

@@ -142,16 +142,23 @@ def exact_blocks(t: int, nrows: int, k: int, rng: np.random.Generator) -> np.nda
     return w.reshape(nrows, nb * bs)
 
 
-def exact_acts(n: int, k: int, rng: np.random.Generator, kind: str = "bf16") -> np.ndarray:
-    """Integer activations in [-16, 16] as f32 [n, k].  kind "q8_0" / "q8_k" adds the one element per 32- / 256-block that makes the CPU's
-    activation quantizer the identity (amax = 127: d = 1, quants == x), placed as tests/test_gpu_parity.py places it."""
-    x = rng.integers(-16, 17, (n, k)).astype(np.float32)
+def exact_acts(n: int, k: int, rng: np.random.Generator, kind: str = "bf16", amp: int = 16, factors=None) -> np.ndarray:
+    """Integer activations in [-amp, amp] as f32 [n, k].  kind "q8_0" / "q8_k" adds the one element per 32- / 256-block that makes the CPU's
+    activation quantizer the identity (amax = 127: d = 1, quants == x), placed as tests/test_gpu_parity.py places it.
+    factors: exponents e to draw from, one per activation block (32 elements, 256 for "q8_k"): the block is multiplied by 2^e, its sentinel
+    becomes +-127 * 2^e, so the CPU's quantizer gives d = 2^e exactly and the same integer quants -- a kernel that pairs a block with
+    another block's d is then wrong, which d = 1 everywhere cannot show."""
+    x = rng.integers(-amp, amp + 1, (n, k)).astype(np.float32)
     if kind == "q8_0":
         x.reshape(n, k // 32, 32)[:, :, 0] = 127.0
     elif kind == "q8_k":
         x.reshape(n, k // 256, 256)[:, :, 3] = -127.0
     else:
         assert kind == "bf16", kind
+    if factors is not None:
+        blk = 256 if kind == "q8_k" else 32
+        e = rng.choice(np.asarray(factors, np.float32), (n, k // blk))
+        x = (x.reshape(n, k // blk, blk) * np.exp2(e)[:, :, None]).reshape(n, k).astype(np.float32)
     return x
 
 
@@ -180,3 +187,108 @@ EXACT_FORM_KS = {
     _Q.IQ3_XXS: (2048, 4096, 8192),
 }
 EXACT_CANONICAL_K = {t: (384 if BLCK[t] == 32 else 512) for t in _F16_FIELDS}      # rows stay canonical at these K for every type that has a planar form
+
+
+# ------------------------------------------------------------------------------------------------
+# exact data of the per-column (GEMV) tiers: tests/test_gpu_gemv_forms.py
+# ------------------------------------------------------------------------------------------------
+# Those tiers restate the CPU's arithmetic: integer block sums against QUANTIZED activations, one f32 product per block.  With exact_acts'
+# identity-quantized activations (d = 2^e per block, integer quants) every block term is a power of two times an integer, and the terms a
+# kernel may form separately are bounded per element by (|w| + 2 EXACT_MINS) |x|:
+#   Q4_K / Q5_K / Q2_K  d sc sum(q x) and dmin m sum(x), m <= 15        Q4_1 / Q5_1  d sum(q x) and m s, |m| <= 16 / 32 (s = d_x sum(x) as f16)
+#   IQ1_S / IQ1_M       d (2s+1) sum(8 g x) / 8 and d (2s+1) delta sum(x) / 8, 2s+1 <= 15 (in EXACT_UNITs of d / 8)
+# every other type folds its offset into the integer sum.
+EXACT_MINS = {_Q.Q4_K: 15.0, _Q.Q5_K: 15.0, _Q.Q2_K: 15.0, _Q.Q4_1: 16.0, _Q.Q5_1: 32.0, _Q.IQ1_S: 15.0, _Q.IQ1_M: 15.0}
+
+
+def exact_x_unit(x: np.ndarray) -> float:
+    """The largest power of two (<= 1) that every activation is an integer multiple of."""
+    u = 1.0
+    while not np.array_equal(x / u, np.round(x / u)):
+        u /= 2.0
+        assert u >= 2.0 ** -16, "activations are not small dyadic numbers"
+    return u
+
+
+def exact_output_bound(orc, t: int, w: np.ndarray, x: np.ndarray, K: int, dq: np.ndarray | None = None) -> float:
+    """max over (row, token) of sum_k (|w[row, k]| + 2 EXACT_MINS) |x[token, k]|, in units of EXACT_UNIT[t] * exact_x_unit(x).  Every partial
+    sum of ONE output, in any order, is bounded by that output's own sum, so below 2^24 each is an exact f32 -- the per-output form of
+    exact_sum_bound, which takes the maximum over tokens before it sums and is looser for it."""
+    dq = orc.dequantize(t, w, K) if dq is None else dq
+    xi = (np.abs(x).astype(np.float64) / exact_x_unit(x)).T
+    mins = 2.0 * EXACT_MINS.get(t, 0.0)
+    worst = 0.0
+    for r0 in range(0, dq.shape[0], 2048):                    # (row chunks: the float64 copy of a large matrix is never held whole)
+        wi = np.abs(dq[r0:r0 + 2048].astype(np.float64)) / EXACT_UNIT[t] + mins
+        worst = max(worst, float((wi @ xi).max()))
+    return worst
+
+
+def exact_product_rows(orc, t: int, w: np.ndarray, x: np.ndarray, K: int, dq: np.ndarray | None = None) -> np.ndarray:
+    """exact_product in row chunks (the same numbers; for matrices of ten thousand rows)."""
+    dq = orc.dequantize(t, w, K) if dq is None else dq
+    x64 = x.astype(np.float64)
+    return np.concatenate([(x64 @ dq[r0:r0 + 2048].astype(np.float64).T).astype(np.float32) for r0 in range(0, dq.shape[0], 2048)], axis=1)
+
+
+GEMV_PLANAR_TYPES = (_Q.Q4_K, _Q.Q5_K, _Q.Q6_K, _Q.IQ4_XS, _Q.IQ3_S, _Q.IQ3_XXS, _Q.Q8_0, _Q.Q4_0, _Q.IQ4_NL)
+GEMV_ACT_KIND = {t: ("q8_0" if BLCK[t] == 32 else "q8_k") for t in _F16_FIELDS}      # block size of the activation format the CPU pairs with t
+
+
+# canonical rows that N > 8 sends to the batched canonical tier unless MI355Q_FLAG_FORCE_GEMV is set (csrc/mmq_generic.hip)
+GEMV_CANONICAL_BATCH_TYPES = (_Q.Q4_0, _Q.Q4_1, _Q.Q5_0, _Q.Q5_1, _Q.Q8_0, _Q.IQ4_NL, _Q.Q2_K, _Q.Q3_K, _Q.IQ2_XXS, _Q.IQ2_XS, _Q.IQ2_S, _Q.IQ3_XXS,
+                              _Q.IQ3_S, _Q.IQ1_S, _Q.IQ1_M)
+
+
+def gemv_small_k(t: int) -> int:
+    """The type's smallest planar K: a row is a single partial step of the streaming kernel."""
+    return {_Q.Q6_K: 2048, _Q.IQ3_S: 2048, _Q.IQ3_XXS: 2048, _Q.IQ4_XS: 512}.get(t, 256)
+
+
+def gemv_ring_k(t: int, steps: int) -> int:
+    """A planar K of `steps` steps per row (2048 elements a step, 1024 for Q8_0) whose last step is partial where the type has such a K."""
+    if t in (_Q.Q6_K, _Q.IQ3_S, _Q.IQ3_XXS):
+        return 2048 * steps
+    if t == _Q.Q8_0:
+        return 1024 * (steps - 1) + 256
+    return 2048 * (steps - 1) + (512 if t == _Q.IQ4_XS else 256)
+
+
+def gemv_canonical_ks(t: int) -> tuple:
+    """(smallest K, a K of 65..127 sub-blocks of 32: a lane's second trip is ragged) at which rows of t are canonical."""
+    if BLCK[t] == 32:
+        return 384, 3104                                      # K % 256 != 0; 97 sub-blocks
+    return (768 if t == _Q.IQ4_XS else 512), 2304             # IQ4_XS: 3 / 9 blocks (odd); Q6_K, IQ3_*: K % 2048 != 0; 72 sub-blocks
+
+
+def gemv_amplitude(k: int, scaled: bool) -> tuple:
+    """(amplitude, factor exponents) of the activations at K = k: chosen from the sizes of the formats' integers (largest |w| 254 units, a
+    sentinel of 127 per activation block) so that sum (|w| + 2 mins) |x| of one output stays below 2^24 smallest units -- proven entry by
+    entry in tests/test_exact_data_cpu.py, never read off a kernel's answer."""
+    if k <= 1024:
+        return 16, ((-2, -1, 0, 1, 2) if scaled else None)
+    if k <= 4608:
+        return 8, ((-1, 0, 1) if scaled else None)
+    if k <= 8192:
+        return 4, ((-1, 0) if scaled else None)
+    return 2, ((0, 1) if scaled else None)
+
+
+def _gemv_form_data():
+    ks = {t: set() for t in _F16_FIELDS}
+    for t in GEMV_PLANAR_TYPES:
+        ks[t] |= {gemv_small_k(t), gemv_ring_k(t, 2), gemv_ring_k(t, 3), 2048}
+    for t in (_Q.Q4_K, _Q.Q4_0):
+        ks[t] |= {6144, 12288, 16640, 16384}                  # activation passes 1, 2, 3 of the prologue; column tiles 7 + 1
+    ks[_Q.Q4_K] |= {28672}                                    # column tiles 4 + 3
+    for t in _F16_FIELDS:
+        if t not in (_Q.Q4_K, _Q.Q5_K):                       # (planar at every valid K)
+            ks[t] |= set(gemv_canonical_ks(t))
+    ks[_Q.Q5_0] |= {64}                                       # the row loop above 32768 rows
+    ks[_Q.Q2_K] |= {2048}                                     # a canonical matrix next to planar ones
+    return tuple((t, k) + gemv_amplitude(k, scaled) for t in sorted(ks) for k in sorted(ks[t]) for scaled in (False, True))
+
+
+# (type, K, amplitude, factor exponents or None) of every data set tests/test_gpu_gemv_forms.py draws; tests/test_exact_data_cpu.py proves
+# the 2^24 precondition and the exactness of the CPU arithmetic for each without a GPU
+GEMV_FORM_DATA = _gemv_form_data()
