@@ -285,7 +285,8 @@ typedef struct mi355q_stage {
      * Q's block, V's reuses K's) cannot be matched that way once the plan reorders consumers behind later producers.  Such a caller labels
      * every output with a unique non-zero id (y_id[i] for mats[i].y, sum_id for sum_out, attn->out_id) and every operand with the id of the
      * value it means (x_id, x1_id, attn->q_id / k_id / v_id; 0 = a plain vector complete before the launch): ids then decide, addresses
-     * only give the offset of a sub-vector inside the labelled output.                                                                       */
+     * only give the offset of a sub-vector inside the labelled output.  Any non-zero value is an id, negative ones included.  An x_out vector
+     * has no id: no operand of a later stage can name it, by id or by address (plan_create refuses both).                                    */
     int64_t      y_id[4], sum_id, x_id, x1_id;
     /* OUTPUT FORM.  MI355Q_Y_ROWS (0): y_i = W_i . x, one vector per matrix.  MI355Q_Y_UNARY_MUL: n_mats == 2, same type and m; the stage
      * publishes ONE vector  y = unary(W_0 . x) * (W_1 . x)  of m elements at mats[0].y (id y_id[0]; mats[1].y is unused): UNARY -> MUL of

@@ -1753,7 +1753,10 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
         if (!p) return true;
         auto take = [&](const OutRange & r) { vs.gran = (const Granule *) (uintptr_t) (r.gran_off + (size_t) (p - r.p) + 1); vs.tag_off = r.tag_off; vs.plain = nullptr; };   // (offset + 1: patched to a pointer below)
         if (id != 0) {                                         // labelled operand: the latest output with this id; the addresses give the offset inside it
-            for (size_t i = outs.size(); i-- > 0;) if (outs[i].id == id) { if (p < outs[i].p || p + n > outs[i].p + outs[i].n) return false; take(outs[i]); return true; }
+            for (size_t i = outs.size(); i-- > 0;) {
+                if (outs[i].gran_off == (size_t) -1) continue; // (an x_out vector has no granules and no id a caller could name: stored plainly DURING the launch)
+                if (outs[i].id == id) { if (p < outs[i].p || p + n > outs[i].p + outs[i].n) return false; take(outs[i]); return true; }
+            }
             return false;                                      // no stage produces this value
         }
         // By address: the LATEST earlier output that CONTAINS the operand produced it.  Later outputs that merely overlap it are other tensors to
@@ -2042,6 +2045,9 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
     }
     if (getenv("MI355Q_PLAN_VERBOSE")) {
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        for (size_t si = 0; si < v.size(); ++si) if (v[si].kind == PLAN_K_GEMV)
+            fprintf(stderr, "mi355q plan: gemv stage %zu: k %d, %d rows, workgroups [%d, %d), group %d, x0 %s%s\n", si, v[si].k, v[si].total_rows, v[si].wg_base, v[si].wg_base + v[si].wg_count,
+                    v[si].group, v[si].x0.plain ? "plain" : "granules", (v[si].flags & PLAN_F_DIRECT) ? " direct" : "");
         fprintf(stderr, "mi355q plan: %zu stages, device block %zu bytes; host time: descriptors %.0f us, device block %.0f us, upload + granule reset %.0f us\n",
                 v.size(), block, us(t_create0, t_alloc0), us(t_alloc0, t_alloc1), us(t_alloc1, std::chrono::steady_clock::now()));
     }

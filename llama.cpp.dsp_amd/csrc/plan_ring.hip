@@ -1385,7 +1385,10 @@ int mi355q_ring_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
         if (!p) return true;
         auto take = [&](const OutRange & r) { vs.gran = (const Granule *) (uintptr_t) (r.gran_off + (size_t) (p - r.p) + 1); vs.tag_off = r.tag_off; vs.plain = nullptr; };   // (offset + 1: patched to a pointer below)
         if (id != 0) {                                         // labelled operand: the latest output with this id; the addresses give the offset inside it
-            for (size_t i = outs.size(); i-- > 0;) if (outs[i].id == id) { if (p < outs[i].p || p + n > outs[i].p + outs[i].n) return false; take(outs[i]); return true; }
+            for (size_t i = outs.size(); i-- > 0;) {
+                if (outs[i].gran_off == (size_t) -1) continue; // (an x_out vector has no granules and no id a caller could name: stored plainly DURING the launch)
+                if (outs[i].id == id) { if (p < outs[i].p || p + n > outs[i].p + outs[i].n) return false; take(outs[i]); return true; }
+            }
             return false;                                      // no stage produces this value
         }
         // By address: the LATEST earlier output that CONTAINS the operand produced it.  Later outputs that merely overlap it are other tensors to
@@ -1469,6 +1472,10 @@ int mi355q_ring_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
         if (in.x_out) {
             VecSrc t0, t1; const bool r0 = resolve(in.x, in.k, in.x_id, t0), r1 = resolve(in.x1, in.k, in.x1_id, t1);
             if ((r0 && t0.plain && overlaps(in.x_out, in.k, in.x, in.k)) || (r1 && t1.plain && overlaps(in.x_out, in.k, in.x1, in.k))) { mi355q_set_error("plan_create: x_out overlaps a plain operand of the same stage"); return MI355Q_ERR_SHAPE; }
+        }
+        if (!(in.flags & MI355Q_STAGE_NO_PLAIN)) {
+            VecSrc t0, t1; const bool r0 = resolve(in.x, in.k, in.x_id, t0), r1 = resolve(in.x1, in.k, in.x1_id, t1);
+            for (int i = 0; i < in.n_mats; ++i) if ((r0 && t0.plain && overlaps(in.mats[i].y, in.mats[i].m, in.x, in.k)) || (r1 && t1.plain && overlaps(in.mats[i].y, in.mats[i].m, in.x1, in.k))) { mi355q_set_error("plan_create: an output overlaps a plain operand of the same stage"); return MI355Q_ERR_SHAPE; }
         }
         const bool paired = in.y_kind == MI355Q_Y_UNARY_MUL;
         if (paired && (in.n_mats != 2 || in.mats[0].type != in.mats[1].type || in.mats[0].m != in.mats[1].m ||

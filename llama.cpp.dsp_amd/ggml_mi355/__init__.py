@@ -306,67 +306,85 @@ _STAGE_KV = {"f16": 0, "q8_0": 0x4, "q4_0": 0x8, "q4_1": 0x10, "q5_0": 0x20, "q5
 KV_BLOCK = {"q8_0": (34, Q8_0), "q4_0": (18, Q4_0), "q4_1": (20, Q4_1), "q5_0": (22, Q5_0), "q5_1": (24, Q5_1), "iq4_nl": (18, IQ4_NL)}     # cache type -> (bytes per 32-element block, type id)
 
 
+def _stage_array(stages):
+    """The mi355q_stage array of a Plan's stage list and the objects it points into (keep them alive as long as the array is used).
+    Reads shapes, dtypes and addresses only -- no library call, no device -- so it works on CPU tensors too."""
+    import torch
+    arr = (_Stage * len(stages))()
+    keep = []
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    for i, sd in enumerate(stages):
+        st = _Stage()
+        if isinstance(sd, dict) and "attn" in sd:
+            a = sd["attn"]
+            at = _Attn()
+            for name in ("q", "k", "v", "pos", "freq_factors", "k_cache", "v_cache", "k_dst", "v_dst", "mask", "out", "n_kv_dev"):
+                setattr(at, name, ptr(a.get(name)))
+            rp = dict(n_dims=a["head_dim"], mode=0, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0, beta_fast=32.0, beta_slow=1.0)
+            rp.update(a.get("rope", {}))
+            at.rope = _RopeParams(rp["n_dims"], rp["mode"], rp["n_ctx_orig"], rp["freq_base"], rp["freq_scale"], rp["ext_factor"], rp["attn_factor"], rp["beta_fast"], rp["beta_slow"])
+            for name in ("k_nb_pos", "k_nb_head", "v_nb_pos", "v_nb_dim", "v_nb_head", "v_dst_nb", "n_head", "n_head_kv", "head_dim", "n_kv"):
+                setattr(at, name, int(a[name]))
+            for name in ("q_id", "k_id", "v_id", "out_id"):
+                setattr(at, name, int(a.get(name, 0)))
+            at.mask_f16 = 1 if (a.get("mask") is not None and a["mask"].dtype == torch.float16) else 0
+            at.scale = float(a["scale"])
+            st.kind = STAGE_ATTN; st.attn = C.pointer(at); st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
+            kv = a.get("kv", "f16")
+            if kv not in _STAGE_KV:
+                raise ValueError(f"attn kv must be one of {sorted(_STAGE_KV)}, not {kv!r}")
+            st.flags |= _STAGE_KV[kv]
+            keep.append((a, at))
+        else:
+            if isinstance(sd, dict):
+                ws_, x, ys = sd["ws"], sd["x"], sd["ys"]
+                st.x_kind = sd.get("x_kind", X_PLAIN); st.x_unary = sd.get("unary", UNARY_SILU); st.eps = float(sd.get("eps", 0.0))
+                st.x1 = ptr(sd.get("x1")); st.norm_w = ptr(sd.get("norm_w")); st.sum_out = ptr(sd.get("sum_out")); st.x_out = ptr(sd.get("x_out"))
+                st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
+                st.y_kind = sd.get("y_kind", Y_ROWS); st.y_unary = sd.get("y_unary", UNARY_SILU)
+                st.x_id = int(sd.get("x_id", 0)); st.x1_id = int(sd.get("x1_id", 0)); st.sum_id = int(sd.get("sum_id", 0))
+                y_ids = sd.get("y_ids")
+                if y_ids is not None:
+                    assert len(y_ids) == len(ws_)
+                    for j, v in enumerate(y_ids):
+                        st.y_id[j] = int(v)
+                for t in (sd.get("x1"), sd.get("norm_w"), sd.get("sum_out"), sd.get("x_out")):
+                    assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x.shape[-1])
+            else:
+                ws_, x, ys, depends = sd
+                st.flags = STAGE_DEPENDS if depends else 0
+            k = x.shape[-1]
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == k
+            assert 1 <= len(ws_) <= 4 and len(ws_) == len(ys)
+            for j, (w, y) in enumerate(zip(ws_, ys)):
+                assert w.K == k and w.n_expert == 1 and y.dtype == torch.float32 and y.is_contiguous() and y.numel() == w.M
+                st.mats[j] = _Mat(w.type, w.data.data_ptr(), w.row_bytes, y.data_ptr(), w.M * 4, w.M)
+            st.kind = STAGE_GEMV; st.n_mats = len(ws_); st.x = x.data_ptr(); st.k = k
+            keep.append(sd)
+        arr[i] = st
+    return arr, keep
+
+
 class Plan:
     """A token's dependent chain as ONE persistent launch (mi355q_plan_*).
 
     stages: a list whose entries are
       * (weights: list[QWeight] (<= 4, same K), x: f32 [1, K] or [K], ys: list of f32 [1, M_i] / [M_i], depends)   -- a plain GEMV stage
         (`depends` is accepted for API version 1 and ignored: an x that is an earlier stage's output is found by its address), or
-      * dict(ws=, ys=, x=, x_kind=X_PLAIN|X_NORM|X_UNARY_MUL, x1=None, norm_w=None, eps=0.0, sum_out=None, unary=UNARY_SILU, no_plain=False,
-             y_kind=Y_ROWS|Y_UNARY_MUL (two weights: ys[0] = y_unary(W0 x) * (W1 x), ys[1] unused), y_unary=UNARY_SILU), or
+      * dict(ws=, ys=, x=, x_kind=X_PLAIN|X_NORM|X_UNARY_MUL, x1=None, norm_w=None, eps=0.0, sum_out=None, x_out=None, unary=UNARY_SILU, no_plain=False,
+             y_kind=Y_ROWS|Y_UNARY_MUL (two weights: ys[0] = y_unary(W0 x) * (W1 x), ys[1] unused), y_unary=UNARY_SILU,
+             x_id=0, x1_id=0, y_ids=None (one per weight), sum_id=0   -- value ids, see mi355q_stage in include/mi355q.h; 0: matched by address), or
       * dict(attn=dict(q=, k=, v=, pos=, rope=dict(n_dims=, mode=0, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0,
                        attn_factor=1.0, beta_fast=32.0, beta_slow=1.0), freq_factors=None, k_cache=, v_cache=, k_nb_pos=, k_nb_head=, v_nb_pos=,
                        v_nb_dim=, v_nb_head=, k_dst=, v_dst= (int64 device tensors holding the destination ADDRESSES), v_dst_nb=, mask=None,
-                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16"), no_plain=False)       -- see include/mi355q.h mi355q_attn;
+                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16", q_id=0, k_id=0, v_id=0, out_id=0), no_plain=False)
+        -- see include/mi355q.h mi355q_attn;
         kv="q8_0" / "q4_0" / "q4_1" / "q5_0" / "q5_1" / "iq4_nl": the caches hold blocks of that type (uint8 tensors; MI355Q_STAGE_KV_*, flash layout only).
     The tensors are referenced by address: keep them alive (the Plan holds references) and do not move them."""
 
     def __init__(self, stages, flags: int = 0):
-        torch = _torch()
-        arr = (_Stage * len(stages))()
-        self._keep = []
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        for i, sd in enumerate(stages):
-            st = _Stage()
-            if isinstance(sd, dict) and "attn" in sd:
-                a = sd["attn"]
-                at = _Attn()
-                for name in ("q", "k", "v", "pos", "freq_factors", "k_cache", "v_cache", "k_dst", "v_dst", "mask", "out", "n_kv_dev"):
-                    setattr(at, name, ptr(a.get(name)))
-                rp = dict(n_dims=a["head_dim"], mode=0, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0, beta_fast=32.0, beta_slow=1.0)
-                rp.update(a.get("rope", {}))
-                at.rope = _RopeParams(rp["n_dims"], rp["mode"], rp["n_ctx_orig"], rp["freq_base"], rp["freq_scale"], rp["ext_factor"], rp["attn_factor"], rp["beta_fast"], rp["beta_slow"])
-                for name in ("k_nb_pos", "k_nb_head", "v_nb_pos", "v_nb_dim", "v_nb_head", "v_dst_nb", "n_head", "n_head_kv", "head_dim", "n_kv"):
-                    setattr(at, name, int(a[name]))
-                at.mask_f16 = 1 if (a.get("mask") is not None and a["mask"].dtype == torch.float16) else 0
-                at.scale = float(a["scale"])
-                st.kind = STAGE_ATTN; st.attn = C.pointer(at); st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
-                kv = a.get("kv", "f16")
-                if kv not in _STAGE_KV:
-                    raise ValueError(f"attn kv must be one of {sorted(_STAGE_KV)}, not {kv!r}")
-                st.flags |= _STAGE_KV[kv]
-                self._keep.append((a, at))
-            else:
-                if isinstance(sd, dict):
-                    ws_, x, ys = sd["ws"], sd["x"], sd["ys"]
-                    st.x_kind = sd.get("x_kind", X_PLAIN); st.x_unary = sd.get("unary", UNARY_SILU); st.eps = float(sd.get("eps", 0.0))
-                    st.x1 = ptr(sd.get("x1")); st.norm_w = ptr(sd.get("norm_w")); st.sum_out = ptr(sd.get("sum_out")); st.x_out = ptr(sd.get("x_out"))
-                    st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
-                    st.y_kind = sd.get("y_kind", Y_ROWS); st.y_unary = sd.get("y_unary", UNARY_SILU)
-                    for t in (sd.get("x1"), sd.get("norm_w"), sd.get("sum_out"), sd.get("x_out")):
-                        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x.shape[-1])
-                else:
-                    ws_, x, ys, depends = sd
-                    st.flags = STAGE_DEPENDS if depends else 0
-                k = x.shape[-1]
-                assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == k
-                assert 1 <= len(ws_) <= 4 and len(ws_) == len(ys)
-                for j, (w, y) in enumerate(zip(ws_, ys)):
-                    assert w.K == k and w.n_expert == 1 and y.dtype == torch.float32 and y.is_contiguous() and y.numel() == w.M
-                    st.mats[j] = _Mat(w.type, w.data.data_ptr(), w.row_bytes, y.data_ptr(), w.M * 4, w.M)
-                st.kind = STAGE_GEMV; st.n_mats = len(ws_); st.x = x.data_ptr(); st.k = k
-                self._keep.append(sd)
-            arr[i] = st
+        _torch()
+        arr, self._keep = _stage_array(stages)
         h = C.c_void_p()
         _check(lib().mi355q_plan_create(C.byref(h), arr, len(stages), flags), "plan_create")
         self._h = h

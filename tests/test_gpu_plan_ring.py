@@ -1,7 +1,7 @@
 """The ring engine of the decode plan (csrc/plan_ring.hip, MI355Q_PLAN_ENGINE=ring), run on the cases of the register engine's tests.
 
-The engine is chosen once per process, so every case runs in ONE fresh interpreter started with MI355Q_PLAN_ENGINE=ring; it prints a PASS / FAIL
-line per case and each test here asserts its own line.  What the child runs:
+The engine is chosen once per process, so every case runs in ONE fresh interpreter started with MI355Q_PLAN_ENGINE=ring (tests/ring_child.py);
+it prints a PASS / FAIL line per case and each test here asserts its own line.  What the child runs:
   * the GEMV prologues and output forms of tests/test_gpu_plan.py (X_PLAIN, X_NORM with x1 / sum_out / x_out, X_UNARY_MUL, Y_UNARY_MUL, NO_PLAIN,
     a mixed-type group, epoch wrap): bit-identical to mul_mat on the node ops' activation vector, as there;
   * the f16 attention cases of tests/test_gpu_plan_attn_forms.py, short last splits and empty ones included.  The ring engine has one attention
@@ -9,14 +9,11 @@ line per case and each test here asserts its own line.  What the child runs:
     held to the float64 bound -- the flash-layout single-split cases too, where the register engine follows the CPU's F16 accumulator -- with the
     stored rows bit-exact and the two garbage fillings giving the same bits.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import PKG, ROOT
+import oracle
+from ring_child import run_ring_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -40,16 +37,12 @@ NKV_CASES = ["nkv-pos255-win256", "nkv-pos700-win704", "nkv-pos0-win1", "nkv-pos
              "nkv_rows-win5", "nkv_rows-win301"]
 ALL = GEMV_CASES + ATTN_CASES + ROPE_CASES + MASK_CASES + NKV_CASES
 
-CHILD = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[2], sys.argv[3]]
-import numpy as np, torch
-import ggml_mi355 as G
-import oracle
-import test_gpu_plan as P
-import test_gpu_plan_attn_forms as A
+GEMV_KINDS = ("prologues", "y_unary_mul", "no_plain", "mixed_type_group", "x_out", "epoch_wrap", "attention_stage_against_the_node_ops",
+              "stage_behind_attention")
 
-def gemv(name):
+
+def gemv(G, torch, name):
+    import test_gpu_plan as P
     t = {"q4_K": oracle.Q4_K, "q6_K": oracle.Q6_K, "q8_0": oracle.Q8_0}
     kind, _, rest = name.partition("-")
     if kind == "prologues": return P.test_norm_and_unary_prologues_match_the_node_ops(G, torch, t[rest])
@@ -63,7 +56,9 @@ def gemv(name):
     if kind == "stage_behind_attention": return P.test_stage_behind_attention_skips_the_attention_workgroups(G, torch, 96 if rest == "one_split" else 600)
     raise KeyError(name)
 
-def attn(name):
+
+def attn(G, torch, name):
+    import test_gpu_plan_attn_forms as A
     if name.startswith("nkv_rows-win"):
         w = int(name[len("nkv_rows-win"):])
         case = A.Case(G, torch, 32, 8, 128, 1024, w - 1, "rows_v", mask="f32", n_kv_dev=w, seed=A.seed_of("rows_dev", w))
@@ -95,43 +90,15 @@ def attn(name):
     finally:
         case.close()
 
-# a plan that reports a non-zero status (a timed-out poll) ends the run: no further GPU work after it
-aborted = []
-_status = G.Plan.status
-def _watched_status(self):
-    st = _status(self)
-    if st != 0:
-        aborted.append(st)
-    return st
-G.Plan.status = _watched_status
 
-names = sys.argv[4].split(",")
-for i, name in enumerate(names):
-    try:
-        r = gemv(name) if name.split("-")[0] in ("prologues", "y_unary_mul", "no_plain", "mixed_type_group", "x_out", "epoch_wrap",
-                                                  "attention_stage_against_the_node_ops", "stage_behind_attention") else attn(name)
-        print("PASS", name, "" if r is None else f"{r:.3e}", flush=True)
-    except Exception as e:
-        print("FAIL", name, type(e).__name__, str(e)[:400].replace(chr(10), " "), flush=True)
-    if aborted:
-        for rest in names[i + 1:]:
-            print("FAIL", rest, "not run: an earlier plan reported status", aborted[0], flush=True)
-        break
-"""
+def run_ring_case(G, torch, name):
+    """What tests/ring_child.py calls per name in the ring engine's process."""
+    return gemv(G, torch, name) if name.split("-")[0] in GEMV_KINDS else attn(G, torch, name)
 
 
 @pytest.fixture(scope="module")
 def ring_results():
-    env = dict(os.environ, MI355Q_PLAN_ENGINE="ring")
-    r = subprocess.run([sys.executable, "-c", CHILD, str(ROOT), str(PKG), str(ROOT / "tests"), ",".join(ALL)], env=env, capture_output=True,
-                       text=True, timeout=900)
-    lines = {}
-    for ln in r.stdout.splitlines():
-        parts = ln.split(" ", 2)
-        if len(parts) >= 2 and parts[0] in ("PASS", "FAIL"):
-            lines[parts[1]] = ln
-    print(r.stdout[-4000:])
-    return r.returncode, lines, r.stderr[-3000:]
+    return run_ring_cases("test_gpu_plan_ring", ALL)[:3]
 
 
 @pytest.mark.parametrize("name", ALL)
