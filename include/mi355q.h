@@ -365,7 +365,7 @@ int mi355q_op_add_rms_norm_mul(const mi355q_tensor *a, const mi355q_tensor *b, c
 int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b, const mi355q_tensor *dst, void *stream);
 /* GGML_OP_FLASH_ATTN_EXT (ggml.c ggml_flash_attn_ext; CPU ggml-cpu/ops.cpp:6690-6905) for an f16 KV cache:
  *   q f32 [DK, N, H, B], k f16 [DK, n_kv, Hk, Bk], v f16 [DV, n_kv, Hv, Bv] (NOT transposed), mask f16 [>= n_kv, >= N] or NULL,
- *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256, n_kv <= 36864.
+ *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256; n_kv <= 36864 on every path but the fused one.
  * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
  * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types are not accepted.
  * k / v may also both hold blocks of one quantized cache type (MI355Q_TYPE_Q8_0, _Q4_0, _Q4_1, _Q5_0, _Q5_1, _IQ4_NL; nb[0] = the block's bytes,
@@ -374,7 +374,27 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
  * (contiguous destination, source rows of whole 32-blocks) with the bytes of the CPU's from_float of the type.
  * workspace (optional, mi355q_op_flash_attn_ext_workspace bytes): with it, a call with few query rows (decode) splits the KV range over
  * several workgroups per row and merges the pieces in a second launch, and a call with >= 16 query rows (prefill) computes scores,
- * softmax and P V on the matrix-core kernels with the scores of the batch in the workspace; without it every row is one workgroup.   */
+ * softmax and P V on the matrix-core kernels with the scores of the batch in the workspace; without it every row is one workgroup --
+ * unless the fused kernel takes the call.
+ * The fused kernel (k_flash_attn_mfma) needs no workspace: one launch, scores never leave the registers, any window length.
+ * It takes an f16 cache (or the f16 copy of a quantized one) with DK % 16 == 0, DV % 16 == 0 and data / nb[1..3] of q, k, v multiples of 16
+ * bytes; any mask row stride.  Which calls go to it is decided by MI355Q_FA_FUSED, read on every call:
+ *   0            never: the behaviour of a library without the kernel, MI355Q_ERR_UNSUPPORTED above 36864 positions included;
+ *   1            every call it can take with >= 16 query rows, or with n_kv > 36864;
+ *   unset, auto  with >= 16 query rows where neither the three-step matrix-core path nor the CPU-exact row kernel (n_kv <= 1024, DK % 32 == 0)
+ *                applies (soft-cap, no or too small a workspace, n_kv % 16 != 0, a wide mask stride), or where the three-step path's scores
+ *                N * n_kv * H * B * 4 exceed 256 MiB (the Infinity Cache); and every call with n_kv > 36864, decode included.
+ * mi355q_op_flash_attn_ext_path answers which kernels a call would take (one of MI355Q_FA_PATH_*, or a negative MI355Q_ERR_* with the message
+ * set) from types, shapes, strides and pointer alignment alone: it makes no device call, and mi355q_op_flash_attn_ext decides by calling it.
+ * It was added without a change of MI355Q_API_VERSION: a caller that may meet an older library probes the symbol.                         */
+#define MI355Q_FA_PATH_ROW_SEQ    0   /* one workgroup per query row, the CPU's sequential F16 accumulation (bit-exact)         */
+#define MI355Q_FA_PATH_ROW_F32    1   /* one workgroup per query row, f32 two-pass                                              */
+#define MI355Q_FA_PATH_ROW_SPLIT  2   /* few rows: the KV range split over several workgroups per row, merged by a second launch */
+#define MI355Q_FA_PATH_KV_ROW     3   /* a quantized or bf16 cache, one workgroup per row with the CPU's arithmetic             */
+#define MI355Q_FA_PATH_MFMA3      4   /* K q -> soft_max -> P V on the matrix-core matmul, scores in the workspace              */
+#define MI355Q_FA_PATH_FUSED      5   /* k_flash_attn_mfma                                                                      */
+int mi355q_op_flash_attn_ext_path(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
+                                  const mi355q_tensor *dst, float logit_softcap, int has_workspace, size_t workspace_bytes);
 size_t mi355q_op_flash_attn_ext_workspace(int64_t dv, int64_t n_q, int64_t n_head, int64_t n_batch, int64_t n_kv);
 int mi355q_op_flash_attn_ext(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
                              const mi355q_tensor *dst, float scale, float max_bias, float logit_softcap,

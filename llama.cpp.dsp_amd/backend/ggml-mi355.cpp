@@ -1095,7 +1095,14 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         if (q->nb[0] != 4 || k->nb[0] != (kv_q80 ? kv_bb : 2u) || v->nb[0] != (kv_q80 ? kv_bb : 2u) || !ggml_is_contiguous(op)) return false;
         if (kv_q80 && (k->ne[0] % 32 || v->ne[0] % 32 || k->ne[1] > 8192 || !mi355_q80_canonical(k) || !mi355_q80_canonical(v))) return false;
         if (m && (m->type != GGML_TYPE_F16 || m->nb[0] != 2 || m->ne[0] < k->ne[1] || m->ne[1] < q->ne[1] || m->ne[2] != 1 || m->ne[3] != 1)) return false;
-        return k->ne[0] <= 256 && v->ne[0] <= 256 && k->ne[1] >= 1 && k->ne[1] <= 36864 && q->ne[2] <= 65535 && q->ne[3] <= 65535;
+        if (k->ne[1] > 36864) {                               // beyond the row kernels' window: the fused matrix-core kernel alone -- an f16 cache,
+            // head sizes of whole 16s, rows of q / k / v on 16-byte strides (buffer addresses are 128-byte aligned; the C-ABI checks the views' offsets)
+            auto al16 = [](const struct ggml_tensor * t) { return ((t->nb[1] | t->nb[2] | t->nb[3]) & 15) == 0; };
+            const char * fused = getenv("MI355Q_FA_FUSED");  // (0 keeps the fused kernel away: then the C-ABI refuses such a window)
+            if (fused && *fused && strcmp(fused, "auto") != 0 && atoi(fused) == 0) return false;
+            if (k->type != GGML_TYPE_F16 || v->type != GGML_TYPE_F16 || k->ne[0] % 16 || v->ne[0] % 16 || !al16(q) || !al16(k) || !al16(v)) return false;
+        }
+        return k->ne[0] <= 256 && v->ne[0] <= 256 && k->ne[1] >= 1 && q->ne[2] <= 65535 && q->ne[3] <= 65535;
     }
     case GGML_OP_SOFT_MAX: {
         const struct ggml_tensor * a = op->src[0];

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <string.h>
+
 #include "mi355q_common.h"
 #include "act_quant.cuh"
 #include "fa_quant.cuh"
@@ -1020,6 +1022,10 @@ __global__ void __launch_bounds__(256) k_scale(const TensorD a, const TensorD d,
 
 static int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int) (g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
 
+// fattn_mfma.hip: the fused matrix-core flash attention (k_flash_attn_mfma)
+int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
+                      float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2, void * stream);
+
 } // namespace mi355q
 
 using namespace mi355q;
@@ -1331,9 +1337,34 @@ size_t mi355q_op_flash_attn_ext_workspace(int64_t dv, int64_t n_q, int64_t n_hea
     return (size_t) (8 * n_q * n_head * n_batch * (dv + 2) * 4);            // up to 8 pieces per row
 }
 
-int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
-                             const mi355q_tensor * dst, float scale, float max_bias, float logit_softcap,
-                             void * workspace, size_t workspace_bytes, void * stream) {
+// ---- FLASH_ATTN_EXT: which kernels a call takes.  The rule stands here once: mi355q_op_flash_attn_ext asks this function and nothing else.
+// MI355Q_FA_FUSED is read on every call (tests flip it in-process): 0 = never the fused kernel, 1 = every call it can take with >= 16 query rows
+// or a window above FA_ROW_MAX_KV, unset / auto = the fused kernel where there is neither the three-step matrix-core path nor the CPU-exact seq
+// row kernel (a), where the three-step path's score scratch would not fit the Infinity Cache (b), and above FA_ROW_MAX_KV (c).  DESIGN.md 5.7f.
+constexpr int64_t FA_ROW_MAX_KV = 36864;                       // the per-row kernels keep a row of scores in LDS
+constexpr size_t  FA_SCRATCH_MALL = (size_t) 256 << 20;        // the Infinity Cache
+static int fa_fused_mode() {                                    // -1 auto, 0 off, 1 forced
+    const char * e = getenv("MI355Q_FA_FUSED");
+    if (!e || !*e || !strcmp(e, "auto")) return -1;
+    return atoi(e) != 0 ? 1 : 0;
+}
+static bool fa_exact_mode() {
+    static const bool fa_exact = !(getenv("MI355Q_FA_EXACT") && atoi(getenv("MI355Q_FA_EXACT")) == 0);
+    return fa_exact;
+}
+static bool fa_al16(const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 15) == 0; }
+// a quantized cache under a prefill batch is decoded ONCE into f16 scratch behind the scores (mi355q_op_flash_attn_ext): when, and the scores' bytes
+static bool fa_kvq_as_f16(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, float logit_softcap, int has_workspace, size_t workspace_bytes, size_t * sc_bytes_out) {
+    const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1];
+    if (!(N >= 16 && logit_softcap == 0.0f && has_workspace && DK % 32 == 0 && DV % 32 == 0)) return false;
+    const size_t sc_bytes = ((size_t) N * (size_t) n_kv * (size_t) q->ne[2] * (size_t) q->ne[3] * 4 + 255) & ~(size_t) 255;
+    const size_t kb16 = (size_t) DK * n_kv * k->ne[2] * k->ne[3] * 2, vb16 = (size_t) DV * n_kv * v->ne[2] * v->ne[3] * 2;
+    if (sc_bytes_out) *sc_bytes_out = sc_bytes;
+    return workspace_bytes >= sc_bytes + ((kb16 + 255) & ~(size_t) 255) + vb16;
+}
+
+int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
+                                  const mi355q_tensor * dst, float logit_softcap, int has_workspace, size_t workspace_bytes) {
     if (!q || !k || !v || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: null tensor");
     const bool kv_q80 = k->type == v->type && kv_block_bytes_rt(k->type) != 0;     // a quantized cache: both q8_0, q4_0, q4_1, q5_0, q5_1 or iq4_nl
     const bool kv_bf16 = k->type == MI355Q_T_BF16 && v->type == MI355Q_T_BF16;
@@ -1346,21 +1377,63 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
     if (q->nb[0] != 4 || k->nb[0] != (kv_q80 ? kv_bb : 2) || v->nb[0] != (kv_q80 ? kv_bb : 2) || dst->nb[0] != 4) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: innermost dimensions must be contiguous");
     if (mask && (mask->ne[0] < n_kv || mask->ne[1] < N || mask->nb[0] != 2)) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: mask f16 [>= n_kv, >= N]");
     if (DK > 256 || DV > 256 || DK < 1 || DV < 1) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: head sizes up to 256");
-    if (n_kv > 36864) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 (one row of scores lives in LDS)");
-    if (N == 0 || n_head == 0 || nb3 == 0) return MI355Q_OK;
+    const int mode = fa_fused_mode();
+    // what the fused kernel takes: an f16 cache (or the f16 copy of a quantized one), head sizes of whole 16s, 16-byte aligned rows
+    const bool as_f16 = kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, has_workspace, workspace_bytes, nullptr);
+    const bool f16 = (k->type == 1 && v->type == 1) || as_f16;
+    const bool al = fa_al16(q) && (as_f16 || (fa_al16(k) && fa_al16(v)));       // (the f16 copy is contiguous and starts on a 256-byte boundary of the workspace)
+    const bool fused_ok = f16 && DK % 16 == 0 && DV % 16 == 0 && al;
+    if (n_kv > FA_ROW_MAX_KV) {
+        if (mode == 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 (one row of scores lives in LDS; MI355Q_FA_FUSED=0 keeps the fused kernel away)");
+        if (!fused_ok) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 needs the fused kernel: an f16 cache, head sizes that are multiples of 16, data and nb[1..3] of q / k / v multiples of 16 bytes");
+    }
+    if (N == 0 || n_head == 0 || nb3 == 0) return n_kv > FA_ROW_MAX_KV ? MI355Q_FA_PATH_FUSED : MI355Q_FA_PATH_ROW_F32;      // (nothing to do)
     if (n_kv == 0) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: empty KV window");
     if (n_head > 65535 || nb3 > 65535) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: too many heads / batches");
+    if (n_kv > FA_ROW_MAX_KV) return MI355Q_FA_PATH_FUSED;                                                                     // (c)
+    // Many query rows (prefill) and scratch for the scores: the three steps of the definition on the matrix-core kernels -- scores = K q
+    // (k_mul_mat_f16_mfma), row softmax with the f16 mask (k_soft_max), out = P V with V read transposed (k_mul_mat_f16_mfma<true>).  One
+    // workgroup per row re-streams K and V for every row: 5x slower for a 512-token batch.  A bf16 cache takes the bf16 form of the
+    // kernels directly (its exponent range does not fit f16 scratch); P is rounded to bf16 there, the one deviation from the CPU (DESIGN.md 5.7d).
+    const size_t scratch = (size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4;
+    const bool mfma3 = (f16 || kv_bf16) && N >= 16 && logit_softcap == 0.0f && has_workspace && (as_f16 || workspace_bytes >= scratch) &&
+                       DK % 16 == 0 && DV % 16 == 0 && n_kv % 16 == 0 && al && n_head * nb3 <= 65535 && (!mask || mask->nb[1] == 2 * n_kv);
+    // few rows (decode): split the KV range so that the chip is not left to n_head workgroups with long dependent chains -- unless the window is short
+    // enough for ONE workgroup per row to follow the CPU's sequential F16 accumulation (k_flash_attn_ext, seq): then the result has the CPU's bits
+    // (MI355Q_FA_EXACT=0 keeps the f32 form)
+    const bool seq = fa_exact_mode() && n_kv <= 1024 && DK % 32 == 0;
+    if (fused_ok && N >= 16 && (mode == 1 || (mode < 0 && (mfma3 ? scratch > FA_SCRATCH_MALL : !seq)))) return MI355Q_FA_PATH_FUSED;      // forced, (b), (a)
+    if (mfma3) return MI355Q_FA_PATH_MFMA3;
+    if ((kv_q80 && !as_f16) || kv_bf16) {                    // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
+        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a quantized cache needs head sizes of whole 32-blocks; a quantized or bf16 cache needs n_kv <= 8192");
+        return MI355Q_FA_PATH_KV_ROW;
+    }
+    if (seq) return MI355Q_FA_PATH_ROW_SEQ;
+    int n_split = 1;
+    if (N * n_head * nb3 <= 256 && n_kv >= 256) { n_split = (int) ((n_kv + 127) / 128); if (n_split > 8) n_split = 8; }
+    if (n_split > 1 && (!has_workspace || workspace_bytes < (size_t) (n_split * N * n_head * nb3 * (DV + 2) * 4))) n_split = 1;
+    return n_split > 1 ? MI355Q_FA_PATH_ROW_SPLIT : MI355Q_FA_PATH_ROW_F32;
+}
+
+int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
+                             const mi355q_tensor * dst, float scale, float max_bias, float logit_softcap,
+                             void * workspace, size_t workspace_bytes, void * stream) {
+    const int path = mi355q_op_flash_attn_ext_path(q, k, v, mask, dst, logit_softcap, workspace ? 1 : 0, workspace_bytes);      // every check of types, shapes and limits
+    if (path < 0) return path;
+    const bool kv_q80 = kv_block_bytes_rt(k->type) != 0, kv_bf16 = k->type == MI355Q_T_BF16;
+    const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
+    if (N == 0 || n_head == 0 || nb3 == 0) return MI355Q_OK;
     if (logit_softcap != 0.0f) scale /= logit_softcap;                          // ops.cpp:6757-6759
     uint32_t n_head_log2 = 1; while (2 * n_head_log2 <= (uint32_t) n_head) n_head_log2 *= 2;
     const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
     mi355q_tensor k16, v16;                                   // (a quantized cache under a prefill batch: its f16 copy)
-    if (kv_q80 && N >= 16 && logit_softcap == 0.0f && workspace && DK % 32 == 0 && DV % 32 == 0) {
+    size_t sc_bytes = 0;
+    if (kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, workspace ? 1 : 0, workspace_bytes, &sc_bytes)) {
         // Many query rows: one workgroup per row re-streams (and re-decodes) the cache for every row.  The cache is decoded ONCE into scratch as f16 and the
-        // matrix-core path below takes it (q in f16 against the dequantized K instead of the CPU's Q8_0-quantized q: ~1e-3 of a score, NMSE 1e-6 of the
-        // output; the decode path, N < 16, keeps the CPU's exact arithmetic).
-        const size_t sc_bytes = ((size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4 + 255) & ~(size_t) 255;
+        // matrix-core paths below take it (q in f16 against the dequantized K instead of the CPU's Q8_0-quantized q: ~1e-3 of a score, NMSE 1e-6 of the
+        // output; the decode path, N < 16, keeps the CPU's exact arithmetic).  The recursive call asks mi355q_op_flash_attn_ext_path about the f16 copy.
         const size_t kb16 = (size_t) DK * n_kv * k->ne[2] * k->ne[3] * 2, vb16 = (size_t) DV * n_kv * v->ne[2] * v->ne[3] * 2;
-        if (workspace_bytes >= sc_bytes + ((kb16 + 255) & ~(size_t) 255) + vb16) {
+        {
             __half * kp = (__half *) ((char *) workspace + sc_bytes), * vp = (__half *) ((char *) kp + ((kb16 + 255) & ~(size_t) 255));
 #define DEQ_KVQ(T) { hipLaunchKernelGGL(k_dequant_cache_f16<T>, dim3(grid_for((int64_t) (kb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(k), kp); \
                      hipLaunchKernelGGL(k_dequant_cache_f16<T>, dim3(grid_for((int64_t) (vb16 / 2))), dim3(256), 0, (hipStream_t) stream, to_d(v), vp); }
@@ -1380,15 +1453,9 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
             return mi355q_op_flash_attn_ext(q, &k16, &v16, mask, dst, logit_softcap != 0.0f ? scale * logit_softcap : scale, max_bias, logit_softcap, workspace, sc_bytes, stream);
         }
     }
-    // Many query rows (prefill) and scratch for the scores: the three steps of the definition on the matrix-core kernels -- scores = K q
-    // (k_mul_mat_f16_mfma), row softmax with the f16 mask (k_soft_max), out = P V with V read transposed (k_mul_mat_f16_mfma<true>).  One
-    // workgroup per row (below) re-streams K and V for every row: 5x slower for a 512-token batch.  A bf16 cache takes the bf16 form of the
-    // kernels directly (its exponent range does not fit f16 scratch); P is rounded to bf16 there, the one deviation from the CPU (DESIGN.md 5.7d).
-    auto al16 = [](const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 15) == 0; };
-    const bool mfma = N >= 16 && logit_softcap == 0.0f && workspace && workspace_bytes >= (size_t) N * (size_t) n_kv * (size_t) n_head * (size_t) nb3 * 4 &&
-                      DK % 16 == 0 && DV % 16 == 0 && n_kv % 16 == 0 && al16(q) && al16(k) && al16(v) && n_head * nb3 <= 65535 && (!mask || mask->nb[1] == 2 * n_kv);
-    if (kv_q80 || (kv_bf16 && !mfma)) {                      // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
-        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a quantized cache needs head sizes of whole 32-blocks; a quantized or bf16 cache needs n_kv <= 8192");
+    if (path == MI355Q_FA_PATH_FUSED)                        // one launch, no score scratch (fattn_mfma.hip)
+        return fattn_mfma_launch(q, k, v, mask, dst, scale, max_bias, logit_softcap, m0, m1, n_head_log2, stream) == MI355Q_OK ? MI355Q_OK : (mi355q_set_error("op_flash_attn_ext: fused kernel launch failed"), MI355Q_ERR_HIP);
+    if (path == MI355Q_FA_PATH_KV_ROW) {                     // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
         const size_t lds = (size_t) (2 * n_kv + (kv_bf16 ? DK : 2 * (DK / 32) + DK / 4)) * 4;
         static bool attr_q80[64] = {};
         if (lds > 48 * 1024) {
@@ -1423,7 +1490,7 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
         OPS_LAUNCHED();
     }
     {
-        if (mfma) {
+        if (path == MI355Q_FA_PATH_MFMA3) {
             mi355q_tensor sc; sc.data = workspace; sc.type = 0;
             sc.ne[0] = n_kv; sc.ne[1] = N; sc.ne[2] = n_head; sc.ne[3] = nb3;
             sc.nb[0] = 4; sc.nb[1] = 4 * n_kv; sc.nb[2] = sc.nb[1] * N; sc.nb[3] = sc.nb[2] * n_head;
@@ -1443,14 +1510,10 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
             OPS_LAUNCHED();
         }
     }
-    // few rows (decode): split the KV range so that the chip is not left to n_head workgroups with long dependent chains -- unless the window is short
-    // enough for ONE workgroup per row to follow the CPU's sequential F16 accumulation (k_flash_attn_ext, seq): then the result has the CPU's bits
-    // (MI355Q_FA_EXACT=0 keeps the f32 form)
-    static const bool fa_exact = !(getenv("MI355Q_FA_EXACT") && atoi(getenv("MI355Q_FA_EXACT")) == 0);
-    const int seq = fa_exact && n_kv <= 1024 && DK % 32 == 0 ? 1 : 0;
+    // the row kernels (k_flash_attn_ext): seq, split over the KV range, or plain f32
+    const int seq = path == MI355Q_FA_PATH_ROW_SEQ ? 1 : 0;
     int n_split = 1;
-    if (!seq && N * n_head * nb3 <= 256 && n_kv >= 256) { n_split = (int) ((n_kv + 127) / 128); if (n_split > 8) n_split = 8; }
-    if (n_split > 1 && (!workspace || workspace_bytes < (size_t) (n_split * N * n_head * nb3 * (DV + 2) * 4))) n_split = 1;
+    if (path == MI355Q_FA_PATH_ROW_SPLIT) { n_split = (int) ((n_kv + 127) / 128); if (n_split > 8) n_split = 8; }
     const int64_t chunk = (n_kv + n_split - 1) / n_split;
     const size_t lds = (size_t) (chunk > FA_THREADS ? chunk : FA_THREADS) * 4 + (seq ? (size_t) n_kv * 4 : 0);
     static bool attr_set[64] = {};

@@ -59,7 +59,14 @@ ABI_SYMBOLS = [
     "mi355q_op_rope", "mi355q_op_mul_mat_f", "mi355q_op_get_rows", "mi355q_op_scale", "mi355q_op_cpy_indirect", "mi355q_op_argsort", "mi355q_op_sum_rows",
     "mi355q_graph_capture_begin", "mi355q_graph_capture_end", "mi355q_graph_launch", "mi355q_graph_destroy",
     "mi355q_op_add_rms_norm_mul", "mi355q_op_unary_mul", "mi355q_op_flash_attn_ext", "mi355q_op_flash_attn_ext_workspace",
+    "mi355q_op_flash_attn_ext_path",
 ]
+
+# mi355q_op_flash_attn_ext_path: which kernels a FLASH_ATTN_EXT call takes (include/mi355q.h MI355Q_FA_PATH_*)
+FA_PATH_ROW_SEQ, FA_PATH_ROW_F32, FA_PATH_ROW_SPLIT, FA_PATH_KV_ROW, FA_PATH_MFMA3, FA_PATH_FUSED = range(6)
+FA_PATH_NAMES = {FA_PATH_ROW_SEQ: "row_seq", FA_PATH_ROW_F32: "row_f32", FA_PATH_ROW_SPLIT: "row_split", FA_PATH_KV_ROW: "kv_row",
+                 FA_PATH_MFMA3: "mfma3", FA_PATH_FUSED: "fused"}
+ERR_UNSUPPORTED, ERR_SHAPE = -1, -2
 
 
 class Mi355qError(RuntimeError):
@@ -151,6 +158,8 @@ def lib() -> C.CDLL:
     L.mi355q_op_unary_mul.argtypes = [i32, TP, TP, TP, vp]
     L.mi355q_op_flash_attn_ext.argtypes = [TP, TP, TP, TP, TP, C.c_float, C.c_float, C.c_float, vp, sz, vp]
     L.mi355q_op_flash_attn_ext_workspace.restype = sz; L.mi355q_op_flash_attn_ext_workspace.argtypes = [i64, i64, i64, i64, i64]
+    if hasattr(L, "mi355q_op_flash_attn_ext_path"):
+        L.mi355q_op_flash_attn_ext_path.argtypes = [TP, TP, TP, TP, TP, C.c_float, C.c_int, sz]
     L.mi355q_op_soft_max.argtypes = [TP, TP, TP, C.c_float, C.c_float, vp]
     L.mi355q_op_rope.argtypes = [TP, vp, vp, TP, C.POINTER(_RopeParams), vp]
     L.mi355q_op_mul_mat_f.argtypes = [TP, TP, TP, vp]
@@ -518,6 +527,38 @@ def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_
                                           C.byref(_td(out)), scale, max_bias, logit_softcap, ws.data_ptr() if ws is not None else None, wsb,
                                           _stream(torch)), "op_flash_attn_ext")
     return out
+
+
+def tensor_desc(type_code: int, ne, nb=None, data: int = 0x10000) -> _Tensor:
+    """An mi355q_tensor from numbers alone (ggml order: ne[0] innermost): for questions that read only the descriptor, such as
+    op_flash_attn_ext_path.  `type_code`: 0 f32, 1 f16, 30 bf16 or a cache block type; nb defaults to contiguous rows; `data` is only an address."""
+    ne = list(ne) + [1] * (4 - len(ne))
+    if nb is None:
+        blk = {Q8_0: 34, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, IQ4_NL: 18}
+        nb = [blk[type_code], ne[0] // 32 * blk[type_code]] if type_code in blk else [{0: 4, 1: 2, 30: 2}[type_code]] * 2
+        if type_code not in blk:
+            nb[1] = nb[0] * ne[0]
+        nb += [nb[1] * ne[1], nb[1] * ne[1] * ne[2]]
+    d = _Tensor(); d.data = data; d.type = type_code
+    for i in range(4):
+        d.ne[i] = ne[i]; d.nb[i] = nb[i]
+    return d
+
+
+def op_flash_attn_ext_path(q, k, v, mask=None, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0", workspace_bytes=None) -> int:
+    """Which kernels op_flash_attn_ext would run for these operands: one of FA_PATH_*, or the negative error code the call would return
+    (last_error() has the message).  No device work.  Operands are torch tensors as for op_flash_attn_ext, or descriptors from tensor_desc.
+    `split` = a workspace is passed (of `workspace_bytes`, by default what mi355q_op_flash_attn_ext_workspace asks for)."""
+    def desc(t):
+        if t is None or isinstance(t, _Tensor):
+            return t
+        return _td_q8_0(t, kv) if t.dtype == _torch().uint8 else _td(t)
+    dq, dk, dv, dm = desc(q), desc(k), desc(v), desc(mask)
+    out = tensor_desc(0, [dv.ne[0], dq.ne[2], dq.ne[1], dq.ne[3]])
+    if workspace_bytes is None:
+        workspace_bytes = int(lib().mi355q_op_flash_attn_ext_workspace(dv.ne[0], dq.ne[1], dq.ne[2], dq.ne[3], dk.ne[1])) if split else 0
+    return int(lib().mi355q_op_flash_attn_ext_path(C.byref(dq), C.byref(dk), C.byref(dv), C.byref(dm) if dm is not None else None, C.byref(out),
+                                                   logit_softcap, 1 if split and workspace_bytes > 0 else 0, workspace_bytes))
 
 
 def op_cpy(a, out, kv: str = "q8_0"):
