@@ -366,10 +366,10 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
 /* GGML_OP_FLASH_ATTN_EXT (ggml.c ggml_flash_attn_ext; CPU ggml-cpu/ops.cpp:6690-6905) for an f16 KV cache:
  *   q f32 [DK, N, H, B], k f16 [DK, n_kv, Hk, Bk], v f16 [DV, n_kv, Hv, Bv] (NOT transposed), mask f16 [>= n_kv, >= N] or NULL,
  *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256; n_kv <= 36864 on every path but the fused one.
- * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
+ * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192 on the row kernel -- beyond: MI355Q_FA_KV_DIRECT below): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
  * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types are not accepted.
  * k / v may also both hold blocks of one quantized cache type (MI355Q_TYPE_Q8_0, _Q4_0, _Q4_1, _Q5_0, _Q5_1, _IQ4_NL; nb[0] = the block's bytes,
- * head sizes of whole 32-blocks, n_kv <= 8192): the CPU's arithmetic for that type; with >= 16 query rows and the
+ * head sizes of whole 32-blocks, n_kv <= 8192 -- beyond: MI355Q_FA_KV_DIRECT below): the CPU's arithmetic for that type; with >= 16 query rows and the
  * workspace the cache is decoded once into f16 scratch for the matrix-core path.  mi355q_op_cpy / _indirect store f32 into such a cache
  * (contiguous destination, source rows of whole 32-blocks) with the bytes of the CPU's from_float of the type.
  * workspace (optional, mi355q_op_flash_attn_ext_workspace bytes): with it, a call with few query rows (decode) splits the KV range over
@@ -393,12 +393,31 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
 #define MI355Q_FA_PATH_KV_ROW     3   /* a quantized or bf16 cache, one workgroup per row with the CPU's arithmetic             */
 #define MI355Q_FA_PATH_MFMA3      4   /* K q -> soft_max -> P V on the matrix-core matmul, scores in the workspace              */
 #define MI355Q_FA_PATH_FUSED      5   /* k_flash_attn_mfma                                                                      */
+#define MI355Q_FA_PATH_FUSED_KV   6   /* k_flash_attn_mfma on the cache's own blocks / bf16 rows, no f16 copy (only from ..._path2) */
 int mi355q_op_flash_attn_ext_path(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
                                   const mi355q_tensor *dst, float logit_softcap, int has_workspace, size_t workspace_bytes);
 size_t mi355q_op_flash_attn_ext_workspace(int64_t dv, int64_t n_q, int64_t n_head, int64_t n_batch, int64_t n_kv);
 int mi355q_op_flash_attn_ext(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
                              const mi355q_tensor *dst, float scale, float max_bias, float logit_softcap,
                              void *workspace, size_t workspace_bytes, void *stream);
+/* The same two with flags (added without a change of MI355Q_API_VERSION: probe the symbols); the functions above are these with flags = 0.
+ * MI355Q_FA_KV_DIRECT: the fused kernel may read a quantized or bf16 cache's own rows, decoding blocks on the way into LDS (bf16: both
+ * products on the bf16 matrix-core instruction, q and P rounded to bf16, nothing passes through f16).  For a block type the output equals,
+ * bit for bit, the fused kernel's on the f16 copy of the cache.  "Direct-eligible": k / v of one block type with DK % 32 == 0, DV % 32 == 0
+ * and data / nb[1..3] of k and v even -- or both bf16 with DK % 16 == 0, DV % 16 == 0 and data / nb[1..3] multiples of 16 --, and q's data /
+ * nb[1..3] multiples of 16.  The flag is ignored under MI355Q_FA_FUSED=0 and for calls that are not direct-eligible.  Unset / auto, a
+ * direct-eligible call answers MI355Q_FA_PATH_FUSED_KV (d) with n_kv > 8192, for any number of query rows -- the window the row kernel
+ * refuses; a bf16 prompt the three-step path can take goes there only when its scores exceed 256 MiB -- and (e) with >= 16 query rows where
+ * it has neither the f16 copy nor the three-step path (soft-cap, no or too small a workspace; bf16 also n_kv % 16 != 0 or a wide mask
+ * stride).  MI355Q_FA_FUSED=1: every direct-eligible call with >= 16 rows or n_kv > 8192.  An answer of FUSED_KV does not depend on the
+ * workspace: a caller that gets it may pass none.  Rows at positions >= n_kv are never read; a masked position adds nothing as long as its
+ * dequantized value is finite in f16 (bf16: finite).                                                                                    */
+#define MI355Q_FA_KV_DIRECT       0x1
+int mi355q_op_flash_attn_ext_path2(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
+                                   const mi355q_tensor *dst, float logit_softcap, int has_workspace, size_t workspace_bytes, uint32_t flags);
+int mi355q_op_flash_attn_ext2(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
+                              const mi355q_tensor *dst, float scale, float max_bias, float logit_softcap,
+                              void *workspace, size_t workspace_bytes, void *stream, uint32_t flags);
 int mi355q_op_cpy(const mi355q_tensor *a, const mi355q_tensor *dst, void *stream);
 int mi355q_op_soft_max(const mi355q_tensor *a, const mi355q_tensor *mask, const mi355q_tensor *dst, float scale, float max_bias, void *stream);
 int mi355q_op_rope(const mi355q_tensor *a, const int32_t *pos, const float *freq_factors, const mi355q_tensor *dst,

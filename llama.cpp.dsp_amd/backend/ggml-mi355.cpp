@@ -383,6 +383,23 @@ static void mi355_backend_synchronize(ggml_backend_t backend) {
 }
 
 // ---- residency ops: thin wrappers over mi355q_op_* -- the tensor descriptor is ggml's ne[] / nb[] verbatim
+static mi355q_tensor mi355_td(const struct ggml_tensor * t);
+// FLASH_ATTN_EXT goes through mi355q_op_flash_attn_ext2 with MI355Q_FA_KV_DIRECT (the fused kernel reads a quantized or bf16 cache's own rows,
+// DESIGN.md 5.7f) unless MI355_FA_KV_DIRECT=0
+static uint32_t mi355_fa_flags() {
+    static const uint32_t flags = (getenv("MI355_FA_KV_DIRECT") && atoi(getenv("MI355_FA_KV_DIRECT")) == 0) ? 0u : (uint32_t) MI355Q_FA_KV_DIRECT;
+    return flags;
+}
+// Does this FLASH_ATTN_EXT node take the fused kernel on the cache's own rows when it has no workspace?  The library's rule, asked with the node's
+// descriptors (an answer of FUSED_KV does not depend on the workspace; a view's address may not be known yet: the C-ABI checks it again per call).
+static bool mi355_fa_kv_direct(const struct ggml_tensor * op) {
+    if (!mi355_fa_flags()) return false;
+    const mi355q_tensor q = mi355_td(op->src[0]), k = mi355_td(op->src[1]), v = mi355_td(op->src[2]), d = mi355_td(op);
+    mi355q_tensor m; if (op->src[3]) m = mi355_td(op->src[3]);
+    float softcap; memcpy(&softcap, (const float *) op->op_params + 2, sizeof(float));
+    return mi355q_op_flash_attn_ext_path2(&q, &k, &v, op->src[3] ? &m : nullptr, &d, softcap, 0, 0, mi355_fa_flags()) == MI355Q_FA_PATH_FUSED_KV;
+}
+
 static mi355q_tensor mi355_td(const struct ggml_tensor * t) {
     mi355q_tensor d;
     d.data = t->data;
@@ -455,9 +472,11 @@ static void mi355_glue_op(mi355_backend_ctx * ctx, struct ggml_tensor * dst, int
         memcpy(&softcap, (const float *) dst->op_params + 2, sizeof(float));
         const mi355q_tensor k = mi355_td(dst->src[1]), v = mi355_td(dst->src[2]);
         mi355q_tensor m; if (dst->src[3]) m = mi355_td(dst->src[3]);
-        const size_t ws = mi355q_op_flash_attn_ext_workspace(v.ne[0], a.ne[1], a.ne[2], a.ne[3], k.ne[1]);
-        void * wsp = mi355_workspace(ctx, ws);
-        MQ_CHECK(mi355q_op_flash_attn_ext(&a, &k, &v, dst->src[3] ? &m : nullptr, &d, scale, max_bias, softcap, wsp, ws, ctx->stream));
+        size_t ws = mi355q_op_flash_attn_ext_workspace(v.ne[0], a.ne[1], a.ne[2], a.ne[3], k.ne[1]);
+        const uint32_t fl = mi355_fa_flags();                 // (asked before the workspace is sized: the fused kernel on the cache's own rows needs none)
+        if (fl && mi355q_op_flash_attn_ext_path2(&a, &k, &v, dst->src[3] ? &m : nullptr, &d, softcap, 1, ws, fl) == MI355Q_FA_PATH_FUSED_KV) ws = 0;
+        void * wsp = ws ? mi355_workspace(ctx, ws) : nullptr;
+        MQ_CHECK(mi355q_op_flash_attn_ext2(&a, &k, &v, dst->src[3] ? &m : nullptr, &d, scale, max_bias, softcap, wsp, ws, ctx->stream, fl));
     } break;
     case GGML_OP_SCALE: {
         float sc; memcpy(&sc, dst->op_params, sizeof(float));
@@ -1090,12 +1109,15 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         const bool kv_bf16 = k->type == GGML_TYPE_BF16 && v->type == GGML_TYPE_BF16;          // a bf16 cache: the same kernel's bf16 form, or the matrix cores for a batch
         const size_t kv_bb = ggml_type_size(k->type);                                          // (bytes per 32-element block)
         if (q->type != GGML_TYPE_F32 || !((k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16) || kv_q80 || kv_bf16) || op->type != GGML_TYPE_F32) return false;
-        if (kv_bf16 && k->ne[1] > 8192) return false;
+        // above 8192 positions a quantized or bf16 cache has the fused kernel on its own rows alone (MI355Q_FA_KV_DIRECT; not under MI355Q_FA_FUSED=0)
+        const bool direct = (kv_q80 || kv_bf16) && k->ne[1] > 8192 && mi355_operand_ok(q) && mi355_operand_ok(k) && mi355_operand_ok(v) &&
+                            (!m || m->type == GGML_TYPE_F16) && mi355_fa_kv_direct(op);
+        if (kv_bf16 && k->ne[1] > 8192 && !direct) return false;
         if (!mi355_operand_ok(q) || !mi355_operand_ok(k) || !mi355_operand_ok(v) || (m && !mi355_operand_ok(m))) return false;
         if (q->nb[0] != 4 || k->nb[0] != (kv_q80 ? kv_bb : 2u) || v->nb[0] != (kv_q80 ? kv_bb : 2u) || !ggml_is_contiguous(op)) return false;
-        if (kv_q80 && (k->ne[0] % 32 || v->ne[0] % 32 || k->ne[1] > 8192 || !mi355_q80_canonical(k) || !mi355_q80_canonical(v))) return false;
+        if (kv_q80 && (k->ne[0] % 32 || v->ne[0] % 32 || (k->ne[1] > 8192 && !direct) || !mi355_q80_canonical(k) || !mi355_q80_canonical(v))) return false;
         if (m && (m->type != GGML_TYPE_F16 || m->nb[0] != 2 || m->ne[0] < k->ne[1] || m->ne[1] < q->ne[1] || m->ne[2] != 1 || m->ne[3] != 1)) return false;
-        if (k->ne[1] > 36864) {                               // beyond the row kernels' window: the fused matrix-core kernel alone -- an f16 cache,
+        if (k->ne[1] > 36864 && !direct) {                    // beyond the row kernels' window: the fused matrix-core kernel alone -- an f16 cache,
             // head sizes of whole 16s, rows of q / k / v on 16-byte strides (buffer addresses are 128-byte aligned; the C-ABI checks the views' offsets)
             auto al16 = [](const struct ggml_tensor * t) { return ((t->nb[1] | t->nb[2] | t->nb[3]) & 15) == 0; };
             const char * fused = getenv("MI355Q_FA_FUSED");  // (0 keeps the fused kernel away: then the C-ABI refuses such a window)

@@ -1,269 +1,10 @@
-// fattn_mfma.hip -- k_flash_attn_mfma: FLASH_ATTN_EXT for many query rows in ONE launch on the matrix cores, gfx950 only.
-//
-//   dst[:, h, t, b] = softmax_j(softcap(scale * k_j . f16(q_t)) + slope_h * mask[t][j]) . v_j        f16 K / V, f32 q, f16 mask or none, f32 dst
-//
-// One 256-thread workgroup per (64 query rows, head, batch); wave w owns rows 16 w .. 16 w + 15 and keeps their q fragments in registers.  The
-// window is walked in tiles of 64 positions: the K and the V tile are copied into LDS as they lie in memory (rows padded against bank conflicts),
-//   S^T[j][t] = sum_e K[j][e] q[t][e]        v_mfma_f32_16x16x32_f16, A = K rows from LDS, B = q fragment      (C: lane holds t = lane & 15,
-//                                                                                                               j = 16 blk + 4 (lane >> 4) + r)
-//   online softmax in f32 per row t (the four lanes lane & 15 == t hold its 64 scores): running maximum, running sum, O rescaled per tile,
-//   O^T[e][t] += sum_j V[j][e] P[t][j]       A = V read TRANSPOSED from LDS (ds_read_b64_tr_b16), B = P rounded to f16.
-// The sum index of an MFMA may be walked in any order as long as both operands agree: k element i of lane group g is position
-// 16 (2 s + (i >> 2)) + 4 g + (i & 3) of the tile, which is where the C layout of S^T left the scores -- P never leaves its registers, and the
-// transposed read delivers exactly V[those four positions][e] per lane.  No score scratch, no workspace, no global atomics.
-//
-// A tile whose mask is -inf for all of the workgroup's query rows is neither loaded nor computed (the causal half of a prompt): a first pass over
-// the mask rows leaves one bit per tile in LDS.  Tiles past that bitmap's capacity (FA_MAP_WORDS * 32 tiles) are simply taken as live.
-// Inside a live tile a masked position has probability exactly 0 and its score is replaced, not added to: the contract is the one of the other
-// matrix-core paths, finite cache rows.  Rows of the tile past n_kv and head elements past DK are zero in LDS, never garbage.
-#include "mi355q_common.h"
-
-#include <math.h>
+// fattn_mfma.hip -- the launcher of k_flash_attn_mfma (fattn_mfma.cuh) and its f16 instantiations.
+#include "fattn_mfma.cuh"
 
 namespace mi355q {
 
-typedef _Float16 fam_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fam_h4 __attribute__((ext_vector_type(4)));
-typedef float    fam_f4 __attribute__((ext_vector_type(4)));
-
-constexpr int FAM_T = 64;                       // query rows per workgroup and positions per tile
-constexpr int FAM_MAP_WORDS = 1024;             // live-tile bitmap: 32768 tiles = 2 Mi positions (beyond: live)
-
-struct FamArgs {
-    const char * q, * k, * v, * m; char * d;
-    int64_t q_nb[4], k_nb[4], v_nb[4], d_nb[4], m_nb1;
-    int64_t N, n_kv;
-    int DK, DV, gqa_k, gqa_v, bq_k, bq_v;       // heads of q per head of k / v, batches of q per batch of k / v
-    int map_words;
-    float scale, softcap, max_bias, m0, m1; uint32_t n_head_log2;
-};
-
-__device__ __forceinline__ fam_h4 fam_read_tr(const uint8_t * p) {
-    typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-    typedef __attribute__((address_space(3))) fp16x4 lds_h4;
-    const fp16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4 *) (uintptr_t) p);      // (the LDS offset is the low half of the flat address)
-    return __builtin_bit_cast(fam_h4, x);
-}
-
-// DKB / DVB: the head sizes rounded up to 64, 128 or 256 -- they size the register arrays; the true sizes are run-time values
-template <int DKB, int DVB>
-__global__ void __launch_bounds__(256) k_flash_attn_mfma(const FamArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t fam_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
-    const int64_t N = a.N, n_kv = a.n_kv, n0 = (int64_t) blockIdx.x * FAM_T;
-    const int h = blockIdx.y, b = blockIdx.z, DK = a.DK, DV = a.DV;
-    const int dk32 = (DK + 31) & ~31;                                        // the K tile's row in LDS: whole 32-element MFMA steps, the tail zero
-    const int rowK = 2 * dk32 + 16, rowV = 2 * DV + 32;                      // bytes; K read as b128 down 16 rows, V by the transposed b64 read
-    uint32_t * live = (uint32_t *) fam_lds;
-    uint8_t * Ks = fam_lds + 4 * a.map_words, * Vs = Ks + FAM_T * rowK;
-    const int64_t n_tiles = (n_kv + FAM_T - 1) / FAM_T;
-    const char * kb = a.k + (h / a.gqa_k) * a.k_nb[2] + (b / a.bq_k) * a.k_nb[3];
-    const char * vb = a.v + (h / a.gqa_v) * a.v_nb[2] + (b / a.bq_v) * a.v_nb[3];
-    const bool m_vec8 = a.m && ((((uintptr_t) a.m) | (uintptr_t) a.m_nb1) & 7) == 0;
-
-    // ---- which tiles are live: wave w looks at tiles w, w + 4, ..; lane = query row of the workgroup
-    if (a.m) {
-        for (int i = tid; i < a.map_words; i += 256) live[i] = 0;
-        __syncthreads();
-        const int64_t lim = n_tiles < (int64_t) a.map_words * 32 ? n_tiles : (int64_t) a.map_words * 32;
-        const bool m_vec16 = ((((uintptr_t) a.m) | (uintptr_t) a.m_nb1) & 15) == 0;
-        const bool row_ok = n0 + lane < N;
-        const char * mr = a.m + (row_ok ? n0 + lane : n0) * a.m_nb1;
-        for (int64_t t = wave; t < lim; t += 4) {
-            const int64_t j0 = t * FAM_T;
-            bool any = false;
-            if (row_ok) {
-                if (m_vec16 && j0 + FAM_T <= n_kv) {
-                    const uint4 * p = (const uint4 *) (mr + 2 * j0);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const uint4 w = p[i];
-                        const uint32_t x[4] = { w.x, w.y, w.z, w.w };
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) any = any || (x[u] & 0xFFFFu) != 0xFC00u || (x[u] >> 16) != 0xFC00u;
-                    }
-                } else {
-                    const int64_t cnt = n_kv - j0 < FAM_T ? n_kv - j0 : FAM_T;
-                    const uint16_t * p = (const uint16_t *) (mr + 2 * j0);
-                    for (int64_t i = 0; i < cnt; ++i) any = any || p[i] != 0xFC00u;
-                }
-            }
-            if (__ballot(any) != 0ull && lane == 0) atomicOr(&live[t >> 5], 1u << (t & 31));
-        }
-        __syncthreads();
-    }
-    auto next_live = [&](int64_t t) -> int64_t {                              // the first live tile >= t (uniform)
-        if (!a.m) return t;
-        while (t < n_tiles && t < (int64_t) a.map_words * 32 && !((live[t >> 5] >> (t & 31)) & 1u)) ++t;
-        return t;
-    };
-
-    // ---- this wave's q rows as B fragments: lane holds row c16, elements 32 kk + 8 g .. + 7, rounded to f16 once
-    const int64_t tq = n0 + 16 * wave + c16, tq_c = tq < N ? tq : N - 1;      // (rows past N repeat the last row and are not stored)
-    fam_h8 qf[DKB / 32];
-    {
-        const char * qp = a.q + tq_c * a.q_nb[1] + h * a.q_nb[2] + b * a.q_nb[3];
-#pragma unroll
-        for (int kk = 0; kk < DKB / 32; ++kk) {
-            const int e = 32 * kk + 8 * g;
-            float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
-            if (e < DK) { f0 = *(const float4 *) (qp + 4 * e); f1 = *(const float4 *) (qp + 4 * e + 16); }
-            qf[kk] = (fam_h8) { (_Float16) f0.x, (_Float16) f0.y, (_Float16) f0.z, (_Float16) f0.w, (_Float16) f1.x, (_Float16) f1.y, (_Float16) f1.z, (_Float16) f1.w };
-        }
-    }
-    const float slope = a.max_bias > 0.0f ? ((uint32_t) h < a.n_head_log2 ? powf(a.m0, (float) (h + 1)) : powf(a.m1, (float) (2 * (h - (int) a.n_head_log2) + 1))) : 1.0f;
-    const char * mrow = a.m ? a.m + tq_c * a.m_nb1 : nullptr;
-
-    fam_f4 O[DVB / 16];
-#pragma unroll
-    for (int c = 0; c < DVB / 16; ++c) O[c] = (fam_f4) { 0.f, 0.f, 0.f, 0.f };
-    float mx = -INFINITY, sum = 0.0f;                                         // the row's running maximum; THIS LANE's part of its running sum
-
-    // ---- staging: thread -> (tile row tid >> 2, 16-byte chunks (tid & 3) + 4 i of that row); the next tile's loads fly under this tile's MFMAs
-    const int srow = tid >> 2, sseg = tid & 3;
-    uint4 kr[DKB / 32], vr[DVB / 32];
-    uint2 mr4[4];                                                             // this lane's 16 mask values of the tile: positions 16 blk + 4 g .. + 3
-    auto fetch = [&](int64_t t) {
-        const int64_t j = t * FAM_T + srow;
-        const bool ok = j < n_kv;
-        const char * kp = kb + (ok ? j : 0) * a.k_nb[1], * vp = vb + (ok ? j : 0) * a.v_nb[1];
-#pragma unroll
-        for (int i = 0; i < DKB / 32; ++i) {
-            const int e = 8 * (sseg + 4 * i);
-            kr[i] = make_uint4(0, 0, 0, 0);
-            if (ok && e < DK) kr[i] = *(const uint4 *) (kp + 2 * e);
-        }
-#pragma unroll
-        for (int i = 0; i < DVB / 32; ++i) {
-            const int e = 8 * (sseg + 4 * i);
-            vr[i] = make_uint4(0, 0, 0, 0);
-            if (ok && e < DV) vr[i] = *(const uint4 *) (vp + 2 * e);
-        }
-        if (mrow) {
-#pragma unroll
-            for (int blk = 0; blk < 4; ++blk) {
-                const int64_t jm = t * FAM_T + 16 * blk + 4 * g;
-                if (m_vec8 && jm + 4 <= n_kv) mr4[blk] = *(const uint2 *) (mrow + 2 * jm);
-                else {
-                    uint32_t x[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x[r] = jm + r < n_kv ? *(const uint16_t *) (mrow + 2 * (jm + r)) : 0xFC00u;
-                    mr4[blk] = make_uint2(x[0] | (x[1] << 16), x[2] | (x[3] << 16));
-                }
-            }
-        }
-    };
-
-    int64_t t = next_live(0);
-    if (t < n_tiles) fetch(t);
-    while (t < n_tiles) {
-        __syncthreads();                                                      // the previous tile's fragments have been read
-#pragma unroll
-        for (int i = 0; i < DKB / 32; ++i) if (8 * (sseg + 4 * i) < dk32) *(uint4 *) (Ks + srow * rowK + 16 * (sseg + 4 * i)) = kr[i];
-#pragma unroll
-        for (int i = 0; i < DVB / 32; ++i) if (8 * (sseg + 4 * i) < DV) *(uint4 *) (Vs + srow * rowV + 16 * (sseg + 4 * i)) = vr[i];
-        uint2 mk[4];
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk) mk[blk] = mr4[blk];
-        const int64_t j0 = t * FAM_T;
-        __syncthreads();
-        t = next_live(t + 1);
-        if (t < n_tiles) fetch(t);
-
-        // ---- S^T = K q: four blocks of 16 positions
-        fam_f4 S[4];
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk) S[blk] = (fam_f4) { 0.f, 0.f, 0.f, 0.f };
-#pragma unroll
-        for (int kk = 0; kk < DKB / 32; ++kk) {
-            if (32 * kk < DK) {
-#pragma unroll
-                for (int blk = 0; blk < 4; ++blk) {
-                    const fam_h8 kf = *(const fam_h8 *) (Ks + (16 * blk + c16) * rowK + 2 * (32 * kk + 8 * g));
-                    S[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[kk], S[blk], 0, 0, 0);
-                }
-            }
-        }
-        // ---- scale, soft-cap, mask; the row's new maximum
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk) {
-            const uint32_t mw[2] = { mk[blk].x, mk[blk].y };
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = S[blk][r] * a.scale;
-                if (a.softcap != 0.0f) s = a.softcap * tanhf(s);
-                if (mrow) {
-                    const uint16_t hb = (uint16_t) (mw[r >> 1] >> (16 * (r & 1)));
-                    const float mv = slope * __half2float(__ushort_as_half(hb));
-                    s = mv == -INFINITY ? -INFINITY : s + mv;                  // (also the positions past n_kv of the last tile)
-                } else if (j0 + 16 * blk + 4 * g + r >= n_kv) s = -INFINITY;
-                S[blk][r] = s;
-                tmax = fmaxf(tmax, s);
-            }
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mnew = fmaxf(mx, tmax);
-        const float alpha = mnew == -INFINITY ? 1.0f : expf(mx - mnew);       // (mx = -inf: exp(-inf) = 0, O and sum are still 0)
-        mx = mnew;
-        sum *= alpha;
-        fam_h8 pf[2];
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = mnew == -INFINITY ? 0.0f : expf(S[blk][r] - mnew);      // a masked position: exp(-inf) = 0 exactly
-                sum += p;
-                pf[blk >> 1][4 * (blk & 1) + r] = (_Float16) p;
-            }
-        // ---- O^T = O^T alpha + V^T P
-#pragma unroll
-        for (int c = 0; c < DVB / 16; ++c) {
-            if (16 * c < DV) {
-                O[c] *= alpha;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const uint8_t * vp = Vs + (32 * s + 4 * g + (c16 >> 2)) * rowV + 2 * (16 * c + 4 * (c16 & 3));
-                    const fam_h4 lo = fam_read_tr(vp), hi = fam_read_tr(vp + 16 * rowV);
-                    const fam_h8 vf = { lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3] };
-                    O[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[s], O[c], 0, 0, 0);
-                }
-            }
-        }
-    }
-    // ---- dst[e][h][t][b] = O^T[e][t] / sum_t; lane holds e = 16 c + 4 g + r
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    if (tq < N) {
-        const float inv = sum > 0.0f ? 1.0f / sum : 0.0f;                     // (a row with every position masked: zeros)
-        char * dp = a.d + h * a.d_nb[1] + tq * a.d_nb[2] + b * a.d_nb[3];
-#pragma unroll
-        for (int c = 0; c < DVB / 16; ++c) {
-            if (16 * c < DV) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) *(float *) (dp + (int64_t) (16 * c + 4 * g + r) * a.d_nb[0]) = O[c][r] * inv;
-            }
-        }
-    }
-}
-
-template <int DKB, int DVB>
-static hipError_t fam_launch_t(const FamArgs & a, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr_set[64] = {};
-    if (lds > 48 * 1024) {
-        int dev = 0; (void) hipGetDevice(&dev); dev = dev >= 0 && dev < 64 ? dev : 0;
-        if (!attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute((const void *) k_flash_attn_mfma<DKB, DVB>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL((k_flash_attn_mfma<DKB, DVB>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-}
-
-// The launcher ops_glue.hip calls once mi355q_op_flash_attn_ext_path has answered MI355Q_FA_PATH_FUSED: shapes, types and alignment are checked there.
+// The launcher ops_glue.hip calls once mi355q_op_flash_attn_ext_path2 has answered MI355Q_FA_PATH_FUSED (f16 k / v) or MI355Q_FA_PATH_FUSED_KV (k / v of
+// one block type, or bf16: the kernel reads the cache's own rows): shapes, types and alignment are checked there.
 // scale is the one applied to the raw dot product (already divided by the soft-cap).
 __attribute__((visibility("hidden")))
 int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
@@ -277,24 +18,20 @@ int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi
     const int64_t n_tiles = (a.n_kv + FAM_T - 1) / FAM_T, words = ((n_tiles + 31) / 32 + 3) & ~(int64_t) 3;      // whole 16 bytes: the tiles behind stay aligned
     a.map_words = mask ? (int) (words < FAM_MAP_WORDS ? words : FAM_MAP_WORDS) : 0;
     a.scale = scale; a.softcap = softcap; a.max_bias = max_bias; a.m0 = m0; a.m1 = m1; a.n_head_log2 = n_head_log2;
+    auto al4 = [](const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 3) == 0 ? 1 : 0; };
+    a.k_al4 = al4(k); a.v_al4 = al4(v);
     const int dk32 = (a.DK + 31) & ~31;
     const size_t lds = (size_t) 4 * a.map_words + (size_t) FAM_T * (2 * dk32 + 16) + (size_t) FAM_T * (2 * a.DV + 32);
     const int64_t gx = (a.N + FAM_T - 1) / FAM_T;
     if (gx > 0x7FFFFFFF) return MI355Q_ERR_UNSUPPORTED;
     const dim3 grid((unsigned) gx, (unsigned) q->ne[2], (unsigned) q->ne[3]);
-    const int kc = a.DK <= 64 ? 0 : a.DK <= 128 ? 1 : 2, vc = a.DV <= 64 ? 0 : a.DV <= 128 ? 1 : 2;
     hipError_t e = hipSuccess;
     hipStream_t st = (hipStream_t) stream;
-    switch (3 * kc + vc) {
-        case 0: e = fam_launch_t<64, 64>(a, grid, lds, st);   break;
-        case 1: e = fam_launch_t<64, 128>(a, grid, lds, st);  break;
-        case 2: e = fam_launch_t<64, 256>(a, grid, lds, st);  break;
-        case 3: e = fam_launch_t<128, 64>(a, grid, lds, st);  break;
-        case 4: e = fam_launch_t<128, 128>(a, grid, lds, st); break;
-        case 5: e = fam_launch_t<128, 256>(a, grid, lds, st); break;
-        case 6: e = fam_launch_t<256, 64>(a, grid, lds, st);  break;
-        case 7: e = fam_launch_t<256, 128>(a, grid, lds, st); break;
-        default: e = fam_launch_t<256, 256>(a, grid, lds, st); break;
+    switch (k->type) {
+        case 1: e = fam_launch_buckets<1>(a, grid, lds, st); break;
+        case MI355Q_TYPE_Q8_0: case MI355Q_TYPE_Q4_0: case MI355Q_TYPE_Q4_1: case MI355Q_T_BF16: e = fam_launch_kva(k->type, a, grid, lds, st); break;
+        case MI355Q_TYPE_Q5_0: case MI355Q_TYPE_Q5_1: case MI355Q_TYPE_IQ4_NL: e = fam_launch_kvb(k->type, a, grid, lds, st); break;
+        default: return MI355Q_ERR_UNSUPPORTED;
     }
     return e == hipSuccess ? MI355Q_OK : MI355Q_ERR_HIP;
 }

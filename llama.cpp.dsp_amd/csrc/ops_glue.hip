@@ -1363,8 +1363,23 @@ static bool fa_kvq_as_f16(const mi355q_tensor * q, const mi355q_tensor * k, cons
     return workspace_bytes >= sc_bytes + ((kb16 + 255) & ~(size_t) 255) + vb16;
 }
 
+static bool fa_even(const mi355q_tensor * t) { return ((((uintptr_t) t->data) | (uintptr_t) t->nb[1] | (uintptr_t) t->nb[2] | (uintptr_t) t->nb[3]) & 1) == 0; }
+// Rule (d), a quantized prompt (>= 16 rows) above FA_KV_ROW_MAX positions that HAS a workspace for the f16 copy: the fused kernel on the cache's own
+// blocks (true) or the copy followed by the f16 rule (false).  Measured (profiles/fa_kv_direct.md): the copy form takes 0.79 - 0.83
+// of the direct form's time at 512 rows over 16384 and 32768 positions, far outside the spread -- the decode between the barriers costs more than
+// one more pass over the window -- so the copy stays where its workspace is there.
+constexpr bool    FA_KVQ_LONG_PROMPT_DIRECT = false;
+constexpr int64_t FA_KV_ROW_MAX = 8192;                        // k_flash_attn_ext_q80 keeps 2 n_kv floats in LDS
+
 int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
                                   const mi355q_tensor * dst, float logit_softcap, int has_workspace, size_t workspace_bytes) {
+    return mi355q_op_flash_attn_ext_path2(q, k, v, mask, dst, logit_softcap, has_workspace, workspace_bytes, 0);
+}
+
+// flags & MI355Q_FA_KV_DIRECT: k_flash_attn_mfma may read a quantized or bf16 cache's own rows (MI355Q_FA_PATH_FUSED_KV) -- rules (d) and (e) of
+// DESIGN.md 5.7f.  Without the flag, under MI355Q_FA_FUSED=0, or for a call that is not direct-eligible, the answer is the one given without it.
+int mi355q_op_flash_attn_ext_path2(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
+                                   const mi355q_tensor * dst, float logit_softcap, int has_workspace, size_t workspace_bytes, uint32_t flags) {
     if (!q || !k || !v || !dst) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: null tensor");
     const bool kv_q80 = k->type == v->type && kv_block_bytes_rt(k->type) != 0;     // a quantized cache: both q8_0, q4_0, q4_1, q5_0, q5_1 or iq4_nl
     const bool kv_bf16 = k->type == MI355Q_T_BF16 && v->type == MI355Q_T_BF16;
@@ -1383,14 +1398,17 @@ int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor *
     const bool f16 = (k->type == 1 && v->type == 1) || as_f16;
     const bool al = fa_al16(q) && (as_f16 || (fa_al16(k) && fa_al16(v)));       // (the f16 copy is contiguous and starts on a 256-byte boundary of the workspace)
     const bool fused_ok = f16 && DK % 16 == 0 && DV % 16 == 0 && al;
+    // "direct-eligible": what the fused kernel takes from a quantized or bf16 cache as it lies
+    const bool direct_ok = (flags & MI355Q_FA_KV_DIRECT) != 0 && mode != 0 && fa_al16(q) &&
+                           ((kv_q80 && DK % 32 == 0 && DV % 32 == 0 && fa_even(k) && fa_even(v)) || (kv_bf16 && DK % 16 == 0 && DV % 16 == 0 && fa_al16(k) && fa_al16(v)));
     if (n_kv > FA_ROW_MAX_KV) {
         if (mode == 0) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 (one row of scores lives in LDS; MI355Q_FA_FUSED=0 keeps the fused kernel away)");
-        if (!fused_ok) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 needs the fused kernel: an f16 cache, head sizes that are multiples of 16, data and nb[1..3] of q / k / v multiples of 16 bytes");
+        if (!fused_ok && !direct_ok) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: n_kv > 36864 needs the fused kernel: an f16 cache, head sizes that are multiples of 16, data and nb[1..3] of q / k / v multiples of 16 bytes");
     }
-    if (N == 0 || n_head == 0 || nb3 == 0) return n_kv > FA_ROW_MAX_KV ? MI355Q_FA_PATH_FUSED : MI355Q_FA_PATH_ROW_F32;      // (nothing to do)
+    if (N == 0 || n_head == 0 || nb3 == 0) return n_kv > FA_ROW_MAX_KV ? (fused_ok ? MI355Q_FA_PATH_FUSED : MI355Q_FA_PATH_FUSED_KV) : MI355Q_FA_PATH_ROW_F32;      // (nothing to do)
     if (n_kv == 0) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: empty KV window");
     if (n_head > 65535 || nb3 > 65535) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: too many heads / batches");
-    if (n_kv > FA_ROW_MAX_KV) return MI355Q_FA_PATH_FUSED;                                                                     // (c)
+    if (n_kv > FA_ROW_MAX_KV && !direct_ok) return MI355Q_FA_PATH_FUSED;                                                       // (c)
     // Many query rows (prefill) and scratch for the scores: the three steps of the definition on the matrix-core kernels -- scores = K q
     // (k_mul_mat_f16_mfma), row softmax with the f16 mask (k_soft_max), out = P V with V read transposed (k_mul_mat_f16_mfma<true>).  One
     // workgroup per row re-streams K and V for every row: 5x slower for a 512-token batch.  A bf16 cache takes the bf16 form of the
@@ -1402,10 +1420,18 @@ int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor *
     // enough for ONE workgroup per row to follow the CPU's sequential F16 accumulation (k_flash_attn_ext, seq): then the result has the CPU's bits
     // (MI355Q_FA_EXACT=0 keeps the f32 form)
     const bool seq = fa_exact_mode() && n_kv <= 1024 && DK % 32 == 0;
+    if (direct_ok) {
+        if (mode == 1 && (N >= 16 || n_kv > FA_KV_ROW_MAX)) return MI355Q_FA_PATH_FUSED_KV;                                     // forced
+        if (n_kv > FA_KV_ROW_MAX) {                                                                                             // (d): the window the row kernel refuses
+            if (kv_bf16 && mfma3) return scratch > FA_SCRATCH_MALL ? MI355Q_FA_PATH_FUSED_KV : MI355Q_FA_PATH_MFMA3;           // (a bf16 prompt follows (b))
+            if (!as_f16 || FA_KVQ_LONG_PROMPT_DIRECT) return MI355Q_FA_PATH_FUSED_KV;
+        } else if (N >= 16 && !as_f16 && !mfma3) return MI355Q_FA_PATH_FUSED_KV;                                                // (e): neither the f16 copy nor the three steps
+    }
+    if (n_kv > FA_ROW_MAX_KV) return MI355Q_FA_PATH_FUSED;                                                                     // (c) for the f16 copy
     if (fused_ok && N >= 16 && (mode == 1 || (mode < 0 && (mfma3 ? scratch > FA_SCRATCH_MALL : !seq)))) return MI355Q_FA_PATH_FUSED;      // forced, (b), (a)
     if (mfma3) return MI355Q_FA_PATH_MFMA3;
     if ((kv_q80 && !as_f16) || kv_bf16) {                    // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
-        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > 8192) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a quantized cache needs head sizes of whole 32-blocks; a quantized or bf16 cache needs n_kv <= 8192");
+        if ((kv_q80 && (DK % 32 || DV % 32)) || n_kv > FA_KV_ROW_MAX) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: a quantized cache needs head sizes of whole 32-blocks; a quantized or bf16 cache needs n_kv <= 8192");
         return MI355Q_FA_PATH_KV_ROW;
     }
     if (seq) return MI355Q_FA_PATH_ROW_SEQ;
@@ -1418,7 +1444,13 @@ int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor *
 int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
                              const mi355q_tensor * dst, float scale, float max_bias, float logit_softcap,
                              void * workspace, size_t workspace_bytes, void * stream) {
-    const int path = mi355q_op_flash_attn_ext_path(q, k, v, mask, dst, logit_softcap, workspace ? 1 : 0, workspace_bytes);      // every check of types, shapes and limits
+    return mi355q_op_flash_attn_ext2(q, k, v, mask, dst, scale, max_bias, logit_softcap, workspace, workspace_bytes, stream, 0);
+}
+
+int mi355q_op_flash_attn_ext2(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
+                              const mi355q_tensor * dst, float scale, float max_bias, float logit_softcap,
+                              void * workspace, size_t workspace_bytes, void * stream, uint32_t flags) {
+    const int path = mi355q_op_flash_attn_ext_path2(q, k, v, mask, dst, logit_softcap, workspace ? 1 : 0, workspace_bytes, flags);      // every check of types, shapes and limits
     if (path < 0) return path;
     const bool kv_q80 = kv_block_bytes_rt(k->type) != 0, kv_bf16 = k->type == MI355Q_T_BF16;
     const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
@@ -1428,7 +1460,7 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
     const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
     mi355q_tensor k16, v16;                                   // (a quantized cache under a prefill batch: its f16 copy)
     size_t sc_bytes = 0;
-    if (kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, workspace ? 1 : 0, workspace_bytes, &sc_bytes)) {
+    if (path != MI355Q_FA_PATH_FUSED_KV && kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, workspace ? 1 : 0, workspace_bytes, &sc_bytes)) {
         // Many query rows: one workgroup per row re-streams (and re-decodes) the cache for every row.  The cache is decoded ONCE into scratch as f16 and the
         // matrix-core paths below take it (q in f16 against the dequantized K instead of the CPU's Q8_0-quantized q: ~1e-3 of a score, NMSE 1e-6 of the
         // output; the decode path, N < 16, keeps the CPU's exact arithmetic).  The recursive call asks mi355q_op_flash_attn_ext_path about the f16 copy.
@@ -1453,7 +1485,7 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor * q, const mi355q_tensor * k, c
             return mi355q_op_flash_attn_ext(q, &k16, &v16, mask, dst, logit_softcap != 0.0f ? scale * logit_softcap : scale, max_bias, logit_softcap, workspace, sc_bytes, stream);
         }
     }
-    if (path == MI355Q_FA_PATH_FUSED)                        // one launch, no score scratch (fattn_mfma.hip)
+    if (path == MI355Q_FA_PATH_FUSED || path == MI355Q_FA_PATH_FUSED_KV)      // one launch, no score scratch (fattn_mfma.cuh); FUSED_KV: on the cache's own blocks / bf16 rows
         return fattn_mfma_launch(q, k, v, mask, dst, scale, max_bias, logit_softcap, m0, m1, n_head_log2, stream) == MI355Q_OK ? MI355Q_OK : (mi355q_set_error("op_flash_attn_ext: fused kernel launch failed"), MI355Q_ERR_HIP);
     if (path == MI355Q_FA_PATH_KV_ROW) {                     // a quantized or bf16 cache: one workgroup per row with the CPU's arithmetic (k_flash_attn_ext_q80)
         const size_t lds = (size_t) (2 * n_kv + (kv_bf16 ? DK : 2 * (DK / 32) + DK / 4)) * 4;

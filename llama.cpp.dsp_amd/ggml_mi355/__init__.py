@@ -59,13 +59,14 @@ ABI_SYMBOLS = [
     "mi355q_op_rope", "mi355q_op_mul_mat_f", "mi355q_op_get_rows", "mi355q_op_scale", "mi355q_op_cpy_indirect", "mi355q_op_argsort", "mi355q_op_sum_rows",
     "mi355q_graph_capture_begin", "mi355q_graph_capture_end", "mi355q_graph_launch", "mi355q_graph_destroy",
     "mi355q_op_add_rms_norm_mul", "mi355q_op_unary_mul", "mi355q_op_flash_attn_ext", "mi355q_op_flash_attn_ext_workspace",
-    "mi355q_op_flash_attn_ext_path",
+    "mi355q_op_flash_attn_ext_path", "mi355q_op_flash_attn_ext_path2", "mi355q_op_flash_attn_ext2",
 ]
 
 # mi355q_op_flash_attn_ext_path: which kernels a FLASH_ATTN_EXT call takes (include/mi355q.h MI355Q_FA_PATH_*)
-FA_PATH_ROW_SEQ, FA_PATH_ROW_F32, FA_PATH_ROW_SPLIT, FA_PATH_KV_ROW, FA_PATH_MFMA3, FA_PATH_FUSED = range(6)
+FA_PATH_ROW_SEQ, FA_PATH_ROW_F32, FA_PATH_ROW_SPLIT, FA_PATH_KV_ROW, FA_PATH_MFMA3, FA_PATH_FUSED, FA_PATH_FUSED_KV = range(7)
 FA_PATH_NAMES = {FA_PATH_ROW_SEQ: "row_seq", FA_PATH_ROW_F32: "row_f32", FA_PATH_ROW_SPLIT: "row_split", FA_PATH_KV_ROW: "kv_row",
-                 FA_PATH_MFMA3: "mfma3", FA_PATH_FUSED: "fused"}
+                 FA_PATH_MFMA3: "mfma3", FA_PATH_FUSED: "fused", FA_PATH_FUSED_KV: "fused_kv"}
+FA_KV_DIRECT = 0x1      # MI355Q_FA_KV_DIRECT: the fused kernel may read a quantized or bf16 cache's own rows (the ...2 entry points)
 ERR_UNSUPPORTED, ERR_SHAPE = -1, -2
 
 
@@ -160,6 +161,9 @@ def lib() -> C.CDLL:
     L.mi355q_op_flash_attn_ext_workspace.restype = sz; L.mi355q_op_flash_attn_ext_workspace.argtypes = [i64, i64, i64, i64, i64]
     if hasattr(L, "mi355q_op_flash_attn_ext_path"):
         L.mi355q_op_flash_attn_ext_path.argtypes = [TP, TP, TP, TP, TP, C.c_float, C.c_int, sz]
+    if hasattr(L, "mi355q_op_flash_attn_ext_path2"):
+        L.mi355q_op_flash_attn_ext_path2.argtypes = [TP, TP, TP, TP, TP, C.c_float, C.c_int, sz, C.c_uint32]
+        L.mi355q_op_flash_attn_ext2.argtypes = [TP, TP, TP, TP, TP, C.c_float, C.c_float, C.c_float, vp, sz, vp, C.c_uint32]
     L.mi355q_op_soft_max.argtypes = [TP, TP, TP, C.c_float, C.c_float, vp]
     L.mi355q_op_rope.argtypes = [TP, vp, vp, TP, C.POINTER(_RopeParams), vp]
     L.mi355q_op_mul_mat_f.argtypes = [TP, TP, TP, vp]
@@ -453,12 +457,12 @@ def _td(t) -> _Tensor:
 
 def _td_q8_0(t, kv: str = "q8_0") -> _Tensor:
     """uint8 torch tensor holding contiguous block rows of the cache type `kv` (KV_BLOCK: 34-byte block_q8_0, 18-byte block_q4_0, ...), shape
-    [..., n / 32 * bb] (<= 4 dims) -> mi355q_tensor of that type with ne[0] = n."""
+    [..., n / 32 * bb] (<= 4 dims; the outer dimensions may be strided) -> mi355q_tensor of that type with ne[0] = n."""
     torch = _torch()
     if kv not in KV_BLOCK:
         raise ValueError(f"kv must be one of {sorted(KV_BLOCK)}, not {kv!r}")
     bb, code = KV_BLOCK[kv]
-    assert t.dtype == torch.uint8 and t.is_contiguous() and 1 <= t.dim() <= 4 and t.shape[-1] % bb == 0
+    assert t.dtype == torch.uint8 and 1 <= t.dim() <= 4 and t.shape[-1] % bb == 0 and (t.is_contiguous() or t.stride(-1) == 1)
     shape = list(t.shape)[::-1] + [1] * (4 - t.dim())
     d = _Tensor(); d.data = t.data_ptr(); d.type = code
     d.ne[0] = shape[0] // bb * 32; d.nb[0] = bb
@@ -466,6 +470,12 @@ def _td_q8_0(t, kv: str = "q8_0") -> _Tensor:
     for i in range(1, 4):
         d.ne[i] = shape[i]
         if i > 1:
+            d.nb[i] = d.nb[i - 1] * shape[i - 1]
+    if not t.is_contiguous():                         # a view whose block rows are whole (head views of one cache buffer): the strides as they are
+        strides = list(t.stride())[::-1]
+        for i in range(1, t.dim()):
+            d.nb[i] = strides[i]
+        for i in range(max(t.dim(), 2), 4):
             d.nb[i] = d.nb[i - 1] * shape[i - 1]
     return d
 
@@ -513,9 +523,11 @@ def op_unary_mul(uop: int, a, b):
     return out
 
 
-def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0"):
+def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0",
+                      kv_direct: bool = False):
     """GGML_OP_FLASH_ATTN_EXT: q f32 [B, H, N, DK] (torch order), k f16 [Bk, Hk, n_kv, DK], v f16 [Bv, Hv, n_kv, DV], mask f16 [>= N, >= n_kv]
-    or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl cache)."""
+    or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl cache).
+    `kv_direct`: mi355q_op_flash_attn_ext2 with MI355Q_FA_KV_DIRECT -- the fused kernel may read such a cache's own rows."""
     torch = _torch()
     out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3]), dtype=torch.float32, device=q.device)
     ws, wsb = (_workspace(torch, int(lib().mi355q_op_flash_attn_ext_workspace(v.shape[3], q.shape[2], q.shape[1], q.shape[0], k.shape[2])), q.device)
@@ -523,9 +535,12 @@ def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_
     tdkv = (lambda t: _td_q8_0(t, kv)) if k.dtype == torch.uint8 else _td      # (uint8: block_q8_0 / block_q4_0 rows, a quantized cache)
     if k.dtype == torch.uint8:
         out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3] // KV_BLOCK[kv][0] * 32), dtype=torch.float32, device=q.device)
-    _check(lib().mi355q_op_flash_attn_ext(C.byref(_td(q)), C.byref(tdkv(k)), C.byref(tdkv(v)), C.byref(_td(mask)) if mask is not None else None,
-                                          C.byref(_td(out)), scale, max_bias, logit_softcap, ws.data_ptr() if ws is not None else None, wsb,
-                                          _stream(torch)), "op_flash_attn_ext")
+    args = (C.byref(_td(q)), C.byref(tdkv(k)), C.byref(tdkv(v)), C.byref(_td(mask)) if mask is not None else None,
+            C.byref(_td(out)), scale, max_bias, logit_softcap, ws.data_ptr() if ws is not None else None, wsb, _stream(torch))
+    if kv_direct:
+        _check(lib().mi355q_op_flash_attn_ext2(*args, FA_KV_DIRECT), "op_flash_attn_ext2")
+    else:
+        _check(lib().mi355q_op_flash_attn_ext(*args), "op_flash_attn_ext")
     return out
 
 
@@ -545,10 +560,12 @@ def tensor_desc(type_code: int, ne, nb=None, data: int = 0x10000) -> _Tensor:
     return d
 
 
-def op_flash_attn_ext_path(q, k, v, mask=None, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0", workspace_bytes=None) -> int:
+def op_flash_attn_ext_path(q, k, v, mask=None, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0", workspace_bytes=None,
+                           kv_direct: bool = False) -> int:
     """Which kernels op_flash_attn_ext would run for these operands: one of FA_PATH_*, or the negative error code the call would return
     (last_error() has the message).  No device work.  Operands are torch tensors as for op_flash_attn_ext, or descriptors from tensor_desc.
-    `split` = a workspace is passed (of `workspace_bytes`, by default what mi355q_op_flash_attn_ext_workspace asks for)."""
+    `split` = a workspace is passed (of `workspace_bytes`, by default what mi355q_op_flash_attn_ext_workspace asks for).
+    `kv_direct`: ask mi355q_op_flash_attn_ext_path2 with MI355Q_FA_KV_DIRECT, as op_flash_attn_ext(kv_direct=True) does."""
     def desc(t):
         if t is None or isinstance(t, _Tensor):
             return t
@@ -557,8 +574,11 @@ def op_flash_attn_ext_path(q, k, v, mask=None, logit_softcap: float = 0.0, split
     out = tensor_desc(0, [dv.ne[0], dq.ne[2], dq.ne[1], dq.ne[3]])
     if workspace_bytes is None:
         workspace_bytes = int(lib().mi355q_op_flash_attn_ext_workspace(dv.ne[0], dq.ne[1], dq.ne[2], dq.ne[3], dk.ne[1])) if split else 0
-    return int(lib().mi355q_op_flash_attn_ext_path(C.byref(dq), C.byref(dk), C.byref(dv), C.byref(dm) if dm is not None else None, C.byref(out),
-                                                   logit_softcap, 1 if split and workspace_bytes > 0 else 0, workspace_bytes))
+    args = (C.byref(dq), C.byref(dk), C.byref(dv), C.byref(dm) if dm is not None else None, C.byref(out),
+            logit_softcap, 1 if split and workspace_bytes > 0 else 0, workspace_bytes)
+    if kv_direct:
+        return int(lib().mi355q_op_flash_attn_ext_path2(*args, FA_KV_DIRECT))
+    return int(lib().mi355q_op_flash_attn_ext_path(*args))
 
 
 def op_cpy(a, out, kv: str = "q8_0"):
