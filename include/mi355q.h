@@ -367,7 +367,7 @@ int mi355q_op_unary_mul(int uop, const mi355q_tensor *a, const mi355q_tensor *b,
  *   q f32 [DK, N, H, B], k f16 [DK, n_kv, Hk, Bk], v f16 [DV, n_kv, Hv, Bv] (NOT transposed), mask f16 [>= n_kv, >= N] or NULL,
  *   dst f32 [DV, H, N, B];  dst = softmax(softcap(scale k.q) + slope_h mask) v,  head sizes <= 256; n_kv <= 36864 on every path but the fused one.
  * k / v may instead both be bf16 (MI355Q_T_BF16; n_kv <= 8192 on the row kernel -- beyond: MI355Q_FA_KV_DIRECT below): q is rounded to bf16 and the scores are ggml_vec_dot_bf16 as on the CPU; with
- * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types are not accepted.
+ * >= 16 query rows and the workspace the matrix-core path rounds P to bf16.  Mixed k / v types need MI355Q_FA_KV_MIXED (below).
  * k / v may also both hold blocks of one quantized cache type (MI355Q_TYPE_Q8_0, _Q4_0, _Q4_1, _Q5_0, _Q5_1, _IQ4_NL; nb[0] = the block's bytes,
  * head sizes of whole 32-blocks, n_kv <= 8192 -- beyond: MI355Q_FA_KV_DIRECT below): the CPU's arithmetic for that type; with >= 16 query rows and the
  * workspace the cache is decoded once into f16 scratch for the matrix-core path.  mi355q_op_cpy / _indirect store f32 into such a cache
@@ -413,6 +413,21 @@ int mi355q_op_flash_attn_ext(const mi355q_tensor *q, const mi355q_tensor *k, con
  * workspace: a caller that gets it may pass none.  Rows at positions >= n_kv are never read; a masked position adds nothing as long as its
  * dequantized value is finite in f16 (bf16: finite).                                                                                    */
 #define MI355Q_FA_KV_DIRECT       0x1
+/* MI355Q_FA_KV_MIXED: k and v may differ in type (-ctk A -ctv B), each of f16, q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl; a pair with bf16 on one
+ * side stays MI355Q_ERR_UNSUPPORTED.  Without the flag every call answers as before: a mixed pair is refused, by the entry points without flags too.  With it,
+ * a same-type call answers what it answers without.  A library from before the flag ignores the bit and refuses the pair with MI355Q_ERR_UNSUPPORTED: that is
+ * the probe (ask mi355q_op_flash_attn_ext_path2 once; nothing else changed, MI355Q_API_VERSION included).  DK % 32 == 0; DV % 32 == 0 under a block V; data and
+ * nb[1..3] of a block side even.  The CPU's arithmetic is separable and so is this one: the scores follow K's type (q to its vec_dot_type, its vec_dot), the
+ * accumulator V's (f16: the F16 accumulator; a block type: F32 over its to_float).  The answers for such a pair:
+ *   >= 16 rows, no soft-cap, the workspace, DV % 32 == 0, an f16 side 16-byte aligned: each block side is decoded once into f16 scratch (an f16 side is read
+ *                as it lies) and the answer is the f16 rule's for that copy (MFMA3, FUSED, or a row kernel);
+ *   >= 16 rows otherwise: FUSED_KV where MI355Q_FA_KV_DIRECT is set too, MI355Q_FA_FUSED is not 0, the pair is built (f16 or q8_0 on at least one side,
+ *                DK and DV in the same bucket <= 64 / <= 128 / <= 256) and q and an f16 side are 16-byte aligned -- bit for bit the f16 fused kernel on the f16
+ *                copies; else KV_ROW up to 8192 positions; else MI355Q_ERR_UNSUPPORTED;
+ *   < 16 rows:   KV_ROW up to 8192 positions, with the CPU's bits as for same-type caches; beyond, FUSED_KV under the same conditions, else
+ *                MI355Q_ERR_UNSUPPORTED.
+ * MI355Q_FA_FUSED=1 forces FUSED_KV where it is available with >= 16 rows or n_kv > 8192; MI355Q_FA_FUSED=0 never reaches the fused kernel.              */
+#define MI355Q_FA_KV_MIXED        0x2
 int mi355q_op_flash_attn_ext_path2(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,
                                    const mi355q_tensor *dst, float logit_softcap, int has_workspace, size_t workspace_bytes, uint32_t flags);
 int mi355q_op_flash_attn_ext2(const mi355q_tensor *q, const mi355q_tensor *k, const mi355q_tensor *v, const mi355q_tensor *mask,

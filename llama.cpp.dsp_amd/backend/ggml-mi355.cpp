@@ -11,7 +11,7 @@
 //   * GGML_OP_MUL_MAT    with quantized src0 (the 19 types of mi355q_type_supported) or f16 / bf16 / f32 src0, f32 src1, f32 dst
 //   * GGML_OP_MUL_MAT_ID with the same quantized src0 types (expert ids stay on the device)
 //   * ADD SUB MUL DIV SCALE, UNARY (SILU RELU SIGMOID TANH NEG ABS), RMS_NORM, CPY CONT DUP (among f32 / f16 / bf16; f32 -> q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl),
-//     GET_ROWS (f32 / f16 / bf16 rows), SOFT_MAX, ROPE, FLASH_ATTN_EXT (f16, bf16 or one quantized cache type for K / V), ARGSORT, SUM_ROWS -- the variants
+//     GET_ROWS (f32 / f16 / bf16 rows), SOFT_MAX, ROPE, FLASH_ATTN_EXT (f16, bf16 or one quantized cache type for K / V, or K and V of different types among f16 and the quantized ones), ARGSORT, SUM_ROWS -- the variants
 //     a llama / mixtral graph uses (mi355_supports_op lists them); so all nine -ctk / -ctv cache types (f32, f16, bf16, q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl) stay resident
 //   * the no-op view ops NONE / RESHAPE / VIEW / PERMUTE / TRANSPOSE on our own buffers
 // everything else stays on the CPU backend.  The fork's own DSP backend (ggml/src/ggml-dsp/ggml-dsp.cpp)
@@ -385,19 +385,39 @@ static void mi355_backend_synchronize(ggml_backend_t backend) {
 // ---- residency ops: thin wrappers over mi355q_op_* -- the tensor descriptor is ggml's ne[] / nb[] verbatim
 static mi355q_tensor mi355_td(const struct ggml_tensor * t);
 // FLASH_ATTN_EXT goes through mi355q_op_flash_attn_ext2 with MI355Q_FA_KV_DIRECT (the fused kernel reads a quantized or bf16 cache's own rows,
-// DESIGN.md 5.7f) unless MI355_FA_KV_DIRECT=0
+// DESIGN.md 5.7f) unless MI355_FA_KV_DIRECT=0, and with MI355Q_FA_KV_MIXED (K and V of different cache types, -ctk A -ctv B) unless
+// MI355_FA_KV_MIXED=0, which restores the refusal of such nodes
 static uint32_t mi355_fa_flags() {
-    static const uint32_t flags = (getenv("MI355_FA_KV_DIRECT") && atoi(getenv("MI355_FA_KV_DIRECT")) == 0) ? 0u : (uint32_t) MI355Q_FA_KV_DIRECT;
+    static const uint32_t flags = ((getenv("MI355_FA_KV_DIRECT") && atoi(getenv("MI355_FA_KV_DIRECT")) == 0) ? 0u : (uint32_t) MI355Q_FA_KV_DIRECT) |
+                                  ((getenv("MI355_FA_KV_MIXED") && atoi(getenv("MI355_FA_KV_MIXED")) == 0) ? 0u : (uint32_t) MI355Q_FA_KV_MIXED);
     return flags;
 }
 // Does this FLASH_ATTN_EXT node take the fused kernel on the cache's own rows when it has no workspace?  The library's rule, asked with the node's
 // descriptors (an answer of FUSED_KV does not depend on the workspace; a view's address may not be known yet: the C-ABI checks it again per call).
 static bool mi355_fa_kv_direct(const struct ggml_tensor * op) {
-    if (!mi355_fa_flags()) return false;
+    if (!(mi355_fa_flags() & MI355Q_FA_KV_DIRECT)) return false;
     const mi355q_tensor q = mi355_td(op->src[0]), k = mi355_td(op->src[1]), v = mi355_td(op->src[2]), d = mi355_td(op);
     mi355q_tensor m; if (op->src[3]) m = mi355_td(op->src[3]);
     float softcap; memcpy(&softcap, (const float *) op->op_params + 2, sizeof(float));
     return mi355q_op_flash_attn_ext_path2(&q, &k, &v, op->src[3] ? &m : nullptr, &d, softcap, 0, 0, mi355_fa_flags()) == MI355Q_FA_PATH_FUSED_KV;
+}
+// A FLASH_ATTN_EXT node over a mixed cache: does the library's rule answer a path for the node's descriptors, with the flags and the workspace
+// mi355_compute_op would pass?  A view's address may not be known yet, and a null address counts as aligned: q and an f16 side whose strides or view
+// offset are not multiples of 16 bytes are asked about at an address that is not either, so that a node is not accepted on an alignment its real
+// address cannot have (a quantized side needs even bytes only, which block rows always are; the C-ABI checks every address again per call).
+static bool mi355_fa_kv_mixed_ok(const struct ggml_tensor * op) {
+    mi355q_tensor q = mi355_td(op->src[0]), k = mi355_td(op->src[1]), v = mi355_td(op->src[2]);
+    const mi355q_tensor d = mi355_td(op);
+    auto pin = [](const struct ggml_tensor * t, mi355q_tensor & td) {
+        if (((t->nb[1] | t->nb[2] | t->nb[3] | t->view_offs) & 15) != 0 && (((uintptr_t) td.data) & 15) == 0) td.data = (void *) ((uintptr_t) td.data + 8);
+    };
+    pin(op->src[0], q);
+    if (op->src[1]->type == GGML_TYPE_F16) pin(op->src[1], k);
+    if (op->src[2]->type == GGML_TYPE_F16) pin(op->src[2], v);
+    mi355q_tensor m; if (op->src[3]) m = mi355_td(op->src[3]);
+    float softcap; memcpy(&softcap, (const float *) op->op_params + 2, sizeof(float));
+    const size_t ws = mi355q_op_flash_attn_ext_workspace(v.ne[0], q.ne[1], q.ne[2], q.ne[3], k.ne[1]);
+    return mi355q_op_flash_attn_ext_path2(&q, &k, &v, op->src[3] ? &m : nullptr, &d, softcap, ws ? 1 : 0, ws, mi355_fa_flags()) >= 0;
 }
 
 static mi355q_tensor mi355_td(const struct ggml_tensor * t) {
@@ -1103,8 +1123,20 @@ static bool mi355_dev_supports_op(ggml_backend_dev_t dev, const struct ggml_tens
         if (op->src[2] && op->src[2]->type != GGML_TYPE_F32) return false;
         return a->ne[0] % 2 == 0;
     }
-    case GGML_OP_FLASH_ATTN_EXT: {                            // f16, bf16 or quantized (K and V of one block type) KV cache, f32 queries, f16 mask; mixed K / V types stay on the CPU
+    case GGML_OP_FLASH_ATTN_EXT: {                            // f16, bf16 or quantized (K and V of one block type) KV cache, f32 queries, f16 mask; mixed K / V types: below
         const struct ggml_tensor * q = op->src[0], * k = op->src[1], * v = op->src[2], * m = op->src[3];
+        // K and V of different types, each f16 or a block type (-ctk A -ctv B; MI355_FA_KV_MIXED=0: refused as before): the per-tensor checks
+        // of the same-type case, then the library's own rule
+        auto mix_side = [](enum ggml_type t) { return t == GGML_TYPE_F16 || mi355_kv_block_type(t); };
+        if (k->type != v->type && mix_side(k->type) && mix_side(v->type) && (mi355_fa_flags() & MI355Q_FA_KV_MIXED)) {
+            if (q->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32) return false;
+            if (!mi355_operand_ok(q) || !mi355_operand_ok(k) || !mi355_operand_ok(v) || (m && !mi355_operand_ok(m))) return false;
+            if (q->nb[0] != 4 || k->nb[0] != ggml_type_size(k->type) || v->nb[0] != ggml_type_size(v->type) || !ggml_is_contiguous(op)) return false;
+            if ((mi355_kv_block_type(k->type) && !mi355_q80_canonical(k)) || (mi355_kv_block_type(v->type) && !mi355_q80_canonical(v))) return false;
+            if (m && (m->type != GGML_TYPE_F16 || m->nb[0] != 2 || m->ne[0] < k->ne[1] || m->ne[1] < q->ne[1] || m->ne[2] != 1 || m->ne[3] != 1)) return false;
+            if (!(k->ne[0] <= 256 && v->ne[0] <= 256 && k->ne[1] >= 1 && q->ne[2] <= 65535 && q->ne[3] <= 65535)) return false;
+            return mi355_fa_kv_mixed_ok(op);
+        }
         const bool kv_q80 = k->type == v->type && mi355_kv_block_type(k->type);       // a quantized cache: the one-workgroup-per-row kernel with the CPU's arithmetic
         const bool kv_bf16 = k->type == GGML_TYPE_BF16 && v->type == GGML_TYPE_BF16;          // a bf16 cache: the same kernel's bf16 form, or the matrix cores for a batch
         const size_t kv_bb = ggml_type_size(k->type);                                          // (bytes per 32-element block)

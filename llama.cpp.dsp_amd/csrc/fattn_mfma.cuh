@@ -17,7 +17,7 @@
 // Inside a live tile a masked position has probability exactly 0 and its score is replaced, not added to: the contract is the one of the other
 // matrix-core paths, finite cache rows.  Rows of the tile past n_kv and head elements past DK are zero in LDS, never garbage.
 //
-// KVT, the cache type (fattn_mfma.hip: f16; fattn_mfma_kva.hip / _kvb.hip: the others, translation units of their own for the build's sake):
+// KVT, the cache type -- VVT is V's where it differs from K's, a mixed cache: fattn_mfma_mx[a-d].hip -- (fattn_mfma.hip: f16; fattn_mfma_kva.hip / _kvb.hip: the others, translation units of their own for the build's sake):
 //   1 (f16)          the text above.
 //   a block type     Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL: only the staging differs.  Thread (row, seg) owns elements 8 seg .. 8 seg + 7 of block i
 //                    of its row: it fetches their raw bytes (8 quant bytes, d, m / one byte of qh where the type has them) packed in four registers
@@ -124,9 +124,11 @@ __device__ __forceinline__ uint4 fam_decode_blk(const uint4 r, int s) {
 }
 
 // DKB / DVB: the head sizes rounded up to 64, 128 or 256 -- they size the register arrays; the true sizes are run-time values
-template <int DKB, int DVB, int KVT = 1>
+// KVT / VVT: the K and the V cache type (VVT != KVT: a mixed cache, DESIGN.md 5.7g -- the K staging follows KVT, the V staging VVT, nothing else differs)
+template <int DKB, int DVB, int KVT = 1, int VVT = KVT>
 __global__ void __launch_bounds__(256) k_flash_attn_mfma(const FamArgs a) {
-    constexpr bool QT = fam_is_blocks(KVT), BF = KVT == MI355Q_T_BF16;
+    constexpr bool QK = fam_is_blocks(KVT), QV = fam_is_blocks(VVT), BF = KVT == MI355Q_T_BF16;
+    static_assert(KVT == VVT || (KVT != MI355Q_T_BF16 && VVT != MI355Q_T_BF16), "a mixed cache has no bf16 side");
     extern __shared__ __attribute__((aligned(16))) uint8_t fam_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
     const int64_t N = a.N, n_kv = a.n_kv, n0 = (int64_t) blockIdx.x * FAM_T;
@@ -207,20 +209,20 @@ __global__ void __launch_bounds__(256) k_flash_attn_mfma(const FamArgs a) {
     auto fetch = [&](int64_t t) {
         const int64_t j = t * FAM_T + srow;
         const bool ok = j < n_kv;
-        if constexpr (QT) row_ok = ok;
+        if constexpr (QK || QV) row_ok = ok;
         const char * kp = kb + (ok ? j : 0) * a.k_nb[1], * vp = vb + (ok ? j : 0) * a.v_nb[1];
 #pragma unroll
         for (int i = 0; i < DKB / 32; ++i) {
             const int e = 8 * (sseg + 4 * i);
             kr[i] = make_uint4(0, 0, 0, 0);
-            if constexpr (QT) { if (ok && 32 * i < DK) fam_fetch_blk<KVT>(kp + kv_block_bytes<KVT>() * i, sseg, a.k_al4 != 0, (kv_block_bytes<KVT>() * i) & 3, kr[i]); }
+            if constexpr (QK) { if (ok && 32 * i < DK) fam_fetch_blk<KVT>(kp + kv_block_bytes<KVT>() * i, sseg, a.k_al4 != 0, (kv_block_bytes<KVT>() * i) & 3, kr[i]); }
             else if (ok && e < DK) kr[i] = *(const uint4 *) (kp + 2 * e);
         }
 #pragma unroll
         for (int i = 0; i < DVB / 32; ++i) {
             const int e = 8 * (sseg + 4 * i);
             vr[i] = make_uint4(0, 0, 0, 0);
-            if constexpr (QT) { if (ok && 32 * i < DV) fam_fetch_blk<KVT>(vp + kv_block_bytes<KVT>() * i, sseg, a.v_al4 != 0, (kv_block_bytes<KVT>() * i) & 3, vr[i]); }
+            if constexpr (QV) { if (ok && 32 * i < DV) fam_fetch_blk<VVT>(vp + kv_block_bytes<VVT>() * i, sseg, a.v_al4 != 0, (kv_block_bytes<VVT>() * i) & 3, vr[i]); }
             else if (ok && e < DV) vr[i] = *(const uint4 *) (vp + 2 * e);
         }
         if (mrow) {
@@ -244,12 +246,12 @@ __global__ void __launch_bounds__(256) k_flash_attn_mfma(const FamArgs a) {
         __syncthreads();                                                      // the previous tile's fragments have been read
 #pragma unroll
         for (int i = 0; i < DKB / 32; ++i) if (8 * (sseg + 4 * i) < dk32) {
-            if constexpr (QT) *(uint4 *) (Ks + srow * rowK + 16 * (sseg + 4 * i)) = row_ok ? fam_decode_blk<KVT>(kr[i], sseg) : make_uint4(0, 0, 0, 0);
+            if constexpr (QK) *(uint4 *) (Ks + srow * rowK + 16 * (sseg + 4 * i)) = row_ok ? fam_decode_blk<KVT>(kr[i], sseg) : make_uint4(0, 0, 0, 0);
             else *(uint4 *) (Ks + srow * rowK + 16 * (sseg + 4 * i)) = kr[i];
         }
 #pragma unroll
         for (int i = 0; i < DVB / 32; ++i) if (8 * (sseg + 4 * i) < DV) {
-            if constexpr (QT) *(uint4 *) (Vs + srow * rowV + 16 * (sseg + 4 * i)) = row_ok ? fam_decode_blk<KVT>(vr[i], sseg) : make_uint4(0, 0, 0, 0);
+            if constexpr (QV) *(uint4 *) (Vs + srow * rowV + 16 * (sseg + 4 * i)) = row_ok ? fam_decode_blk<VVT>(vr[i], sseg) : make_uint4(0, 0, 0, 0);
             else *(uint4 *) (Vs + srow * rowV + 16 * (sseg + 4 * i)) = vr[i];
         }
         uint2 mk[4];
@@ -339,18 +341,18 @@ __global__ void __launch_bounds__(256) k_flash_attn_mfma(const FamArgs a) {
     }
 }
 
-template <int DKB, int DVB, int KVT>
+template <int DKB, int DVB, int KVT, int VVT = KVT>
 static hipError_t fam_launch_t(const FamArgs & a, dim3 grid, size_t lds, hipStream_t st) {
     static bool attr_set[64] = {};
     if (lds > 48 * 1024) {
         int dev = 0; (void) hipGetDevice(&dev); dev = dev >= 0 && dev < 64 ? dev : 0;
         if (!attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute((const void *) k_flash_attn_mfma<DKB, DVB, KVT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            const hipError_t e = hipFuncSetAttribute((const void *) k_flash_attn_mfma<DKB, DVB, KVT, VVT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             if (e != hipSuccess) return e;
             attr_set[dev] = true;
         }
     }
-    hipLaunchKernelGGL((k_flash_attn_mfma<DKB, DVB, KVT>), grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((k_flash_attn_mfma<DKB, DVB, KVT, VVT>), grid, dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
@@ -373,5 +375,38 @@ static hipError_t fam_launch_buckets(const FamArgs & a, dim3 grid, size_t lds, h
 // the other cache types' buckets: fattn_mfma_kva.hip (Q8_0, Q4_0, Q4_1, bf16), fattn_mfma_kvb.hip (Q5_0, Q5_1, IQ4_NL)
 __attribute__((visibility("hidden"))) hipError_t fam_launch_kva(int type, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
 __attribute__((visibility("hidden"))) hipError_t fam_launch_kvb(int type, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
+
+// ---- a mixed cache (K type != V type): the pairs with f16 or Q8_0 on at least one side, head sizes of ONE bucket -- 22 pairs, 66 kernels
+__host__ __device__ constexpr bool fam_mix_anchor(int t) { return t == 1 || t == MI355Q_TYPE_Q8_0; }
+inline bool fam_mix_built(int kt, int vt, int64_t DK, int64_t DV) {
+    const auto seven = [](int t) { return t == 1 || fam_is_blocks(t); };
+    const auto bucket = [](int64_t d) { return d <= 64 ? 0 : d <= 128 ? 1 : 2; };
+    return kt != vt && seven(kt) && seven(vt) && (fam_mix_anchor(kt) || fam_mix_anchor(vt)) && bucket(DK) == bucket(DV);
+}
+template <int KVT, int VVT>
+static hipError_t fam_launch_diag(const FamArgs & a, dim3 grid, size_t lds, hipStream_t st) {
+    if (a.DK <= 64)  return fam_launch_t<64, 64, KVT, VVT>(a, grid, lds, st);
+    if (a.DK <= 128) return fam_launch_t<128, 128, KVT, VVT>(a, grid, lds, st);
+    return fam_launch_t<256, 256, KVT, VVT>(a, grid, lds, st);
+}
+// all block types on the free side of an anchor: ANCHOR_K ? K = ANCHOR, V = type : K = type, V = ANCHOR; WITH_ANCHORS: the other anchor type too
+template <int ANCHOR, bool ANCHOR_K, bool WITH_ANCHORS>
+static hipError_t fam_launch_mix_side(int type, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st) {
+#define FAM_MIX_CASE(T) case T: if constexpr (ANCHOR_K) return fam_launch_diag<ANCHOR, T>(a, grid, lds, st); else return fam_launch_diag<T, ANCHOR>(a, grid, lds, st);
+    if constexpr (WITH_ANCHORS) {
+        constexpr int OTHER = ANCHOR == 1 ? MI355Q_TYPE_Q8_0 : 1;
+        if (type == OTHER) { if constexpr (ANCHOR_K) return fam_launch_diag<ANCHOR, OTHER>(a, grid, lds, st); else return fam_launch_diag<OTHER, ANCHOR>(a, grid, lds, st); }
+    }
+    switch (type) {
+        FAM_MIX_CASE(MI355Q_TYPE_Q4_0) FAM_MIX_CASE(MI355Q_TYPE_Q4_1) FAM_MIX_CASE(MI355Q_TYPE_Q5_0) FAM_MIX_CASE(MI355Q_TYPE_Q5_1) FAM_MIX_CASE(MI355Q_TYPE_IQ4_NL)
+        default: return hipErrorInvalidValue;
+    }
+#undef FAM_MIX_CASE
+}
+// fattn_mfma_mxa.hip (K f16), _mxb.hip (K Q8_0), _mxc.hip (V f16, K of the other five), _mxd.hip (V Q8_0, K of the other five)
+__attribute__((visibility("hidden"))) hipError_t fam_launch_mxa(int vtype, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
+__attribute__((visibility("hidden"))) hipError_t fam_launch_mxb(int vtype, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
+__attribute__((visibility("hidden"))) hipError_t fam_launch_mxc(int ktype, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
+__attribute__((visibility("hidden"))) hipError_t fam_launch_mxd(int ktype, const FamArgs & a, dim3 grid, size_t lds, hipStream_t st);
 
 } // namespace mi355q

@@ -4,8 +4,11 @@
 namespace mi355q {
 
 // The launcher ops_glue.hip calls once mi355q_op_flash_attn_ext_path2 has answered MI355Q_FA_PATH_FUSED (f16 k / v) or MI355Q_FA_PATH_FUSED_KV (k / v of
-// one block type, or bf16: the kernel reads the cache's own rows): shapes, types and alignment are checked there.
+// one block type, or bf16, or a mixed pair of fam_mix_built: the kernel reads the cache's own rows): shapes, types and alignment are checked there.
 // scale is the one applied to the raw dot product (already divided by the soft-cap).
+__attribute__((visibility("hidden")))
+bool fattn_mfma_mix_built(int k_type, int v_type, int64_t DK, int64_t DV) { return fam_mix_built(k_type, v_type, DK, DV); }
+
 __attribute__((visibility("hidden")))
 int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
                       float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2, void * stream) {
@@ -27,6 +30,14 @@ int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi
     const dim3 grid((unsigned) gx, (unsigned) q->ne[2], (unsigned) q->ne[3]);
     hipError_t e = hipSuccess;
     hipStream_t st = (hipStream_t) stream;
+    if (k->type != v->type) {                                                  // a mixed cache (MI355Q_FA_KV_MIXED): the 22 built pairs, one bucket for both head sizes
+        if (!fam_mix_built(k->type, v->type, a.DK, a.DV)) return MI355Q_ERR_UNSUPPORTED;
+        if (k->type == 1) e = fam_launch_mxa(v->type, a, grid, lds, st);
+        else if (k->type == MI355Q_TYPE_Q8_0) e = fam_launch_mxb(v->type, a, grid, lds, st);
+        else if (v->type == 1) e = fam_launch_mxc(k->type, a, grid, lds, st);
+        else e = fam_launch_mxd(k->type, a, grid, lds, st);
+        return e == hipSuccess ? MI355Q_OK : MI355Q_ERR_HIP;
+    }
     switch (k->type) {
         case 1: e = fam_launch_buckets<1>(a, grid, lds, st); break;
         case MI355Q_TYPE_Q8_0: case MI355Q_TYPE_Q4_0: case MI355Q_TYPE_Q4_1: case MI355Q_T_BF16: e = fam_launch_kva(k->type, a, grid, lds, st); break;

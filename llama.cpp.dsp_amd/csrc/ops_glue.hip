@@ -22,16 +22,10 @@
 #include "mi355q_common.h"
 #include "act_quant.cuh"
 #include "fa_quant.cuh"
+#include "fa_row.cuh"                 // TensorD, to_d, FA_THREADS, the f16 side of the row kernels
 
 namespace mi355q {
 
-struct TensorD { char * data; int type; int64_t ne[4]; int64_t nb[4]; };     // device copy of mi355q_tensor (type: 0 f32, 1 f16, 30 bf16)
-
-static TensorD to_d(const mi355q_tensor * t) {
-    TensorD d; d.data = (char *) t->data; d.type = t->type;
-    for (int i = 0; i < 4; ++i) { d.ne[i] = t->ne[i]; d.nb[i] = t->nb[i]; }
-    return d;
-}
 static int64_t nelements(const mi355q_tensor * t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
 static bool same_shape(const mi355q_tensor * a, const mi355q_tensor * b) {
     return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];
@@ -552,7 +546,6 @@ __global__ void __launch_bounds__(256) k_mul_mat_f(const TensorD a, const Tensor
 // f16 before the dot products as the CPU's vec_dot_type conversion does).  Two passes over a row of scores held in LDS instead of the
 // CPU's online update (same mathematics; the CPU accumulates V in f16, this kernel in f32).  Written for correctness and decode sizes:
 // every workgroup streams its head's K and V once.
-constexpr int FA_THREADS = 1024, FA_WAVES = FA_THREADS / 64;      // 16 waves: a decode step has only n_head workgroups, each must hide its own latency
 __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, const TensorD k, const TensorD v, const TensorD m, int has_mask,
                                                         const TensorD d, float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2,
                                                         int n_split, float * __restrict__ part_out, int seq) {
@@ -587,25 +580,7 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
             const int64_t j = j0 + FA_WAVES * c;
             float s = 0.0f;
             if (seq) {
-                // ggml_vec_dot_f16's order (vec.cpp:128-168, AVX2 form; see plan.hip plan_attn_lds step 2): element e = lane + 64 u feeds accumulator
-                // (jj, l) = ((e % 32) / 8, e % 8) of block e / 32 -- lanes L and L ^ 32 own the even and the odd blocks of one accumulator, whose chain
-                // therefore passes between the two halves of the wave; then the tree (a0 + a2) + (a1 + a3), s[l] + s[l + 4], (t0 + t1) + (t2 + t3).
-                const int nblk = (int) (DK >> 5), half = lane >> 5;
-                float acc = 0.0f;
-#pragma unroll
-                for (int blk = 0; blk < 8; ++blk) {                       // (head sizes up to 256: 8 blocks; constant register indices)
-                    if (blk < nblk) {
-                        if (half == (blk & 1)) acc = __builtin_fmaf(kv[c][blk >> 1], qh[blk >> 1], acc);
-                        const float other = __shfl_xor(acc, 32, 64);
-                        if (half != (blk & 1)) acc = other;
-                    }
-                }
-                acc = __fadd_rn(acc, __shfl_xor(acc, 16, 64));            // (a0 + a2) in the j = 0 lanes, (a1 + a3) in the j = 1 lanes
-                acc = __fadd_rn(acc, __shfl_xor(acc, 8, 64));             // s[l]
-                acc = __fadd_rn(acc, __shfl_xor(acc, 4, 64));             // t[i] = s[i] + s[i + 4]
-                acc = __fadd_rn(acc, __shfl_xor(acc, 1, 64));             // t0 + t1 | t2 + t3
-                acc = __fadd_rn(acc, __shfl_xor(acc, 2, 64));
-                s = acc;                                                  // (lane 0)
+                s = fa_dot_f16_seq(kv[c], qh, (int) (DK >> 5), lane);      // ggml_vec_dot_f16's order (fa_row.cuh); lane 0's
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) s += kv[c][u] * qh[u];
@@ -648,17 +623,8 @@ __global__ void __launch_bounds__(FA_THREADS) k_flash_attn_ext(const TensorD q, 
         __syncthreads();
         if (tid < DV) {
             const char * vb = v.data + j_lo * v.nb[1] + hv * v.nb[2] + bv * v.nb[3] + 2 * (int64_t) tid;
-            float acc = 0.0f, S = 0.0f;                                    // acc: an f16 value at all times (VKQ16)
-#pragma unroll 4
-            for (int64_t j = 0; j < n_kv; ++j) {
-                const float vs = fa_s[j], ms = msv[j];
-                if (vs != 0.0f || ms != 1.0f) {                             // (uniform) masked positions are skipped altogether
-                    const float vv = __half2float(*(const __half *) (vb + j * v.nb[1]));
-                    if (ms != 1.0f) acc = f16_round(__fmul_rn(acc, ms));         // ggml_vec_scale_f16
-                    acc = f16_round(__builtin_fmaf(vv, vs, acc));                // ggml_vec_mad_f16
-                    S = __fadd_rn(__fmul_rn(S, ms), vs);
-                }
-            }
+            float acc, S;                                                  // acc: an f16 value at all times (VKQ16)
+            fa_pv_f16_seq(vb, v.nb[1], fa_s, msv, n_kv, acc, S);           // (fa_row.cuh)
             *(float *) (d.data + tid * d.nb[0] + h * d.nb[1] + t * d.nb[2] + b * d.nb[3]) = __fmul_rn(acc, __fdiv_rn(1.0f, S));
         }
         return;
@@ -1025,6 +991,11 @@ static int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)
 // fattn_mfma.hip: the fused matrix-core flash attention (k_flash_attn_mfma)
 int fattn_mfma_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
                       float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2, void * stream);
+// fattn_mix.hip: the CPU-exact row kernel over a mixed cache (k_flash_attn_ext_mix)
+int fattn_mix_launch(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
+                     float scale, float max_bias, float softcap, float m0, float m1, uint32_t n_head_log2, void * stream);
+// fattn_mfma.cuh: the mixed pairs and head-size buckets k_flash_attn_mfma is built for
+bool fattn_mfma_mix_built(int k_type, int v_type, int64_t DK, int64_t DV);
 
 } // namespace mi355q
 
@@ -1371,6 +1342,50 @@ static bool fa_even(const mi355q_tensor * t) { return ((((uintptr_t) t->data) | 
 constexpr bool    FA_KVQ_LONG_PROMPT_DIRECT = false;
 constexpr int64_t FA_KV_ROW_MAX = 8192;                        // k_flash_attn_ext_q80 keeps 2 n_kv floats in LDS
 
+// ---- a mixed cache (MI355Q_FA_KV_MIXED): K and V each of f16 or a block type, K's type != V's
+static bool fa_mix_side(int t) { return t == 1 || kv_block_bytes_rt(t) != 0; }
+// the f16 copy for a prompt: fa_kvq_as_f16's conditions; every block side is decoded with its own type, an f16 side is taken as it lies and must then be
+// 16-byte aligned.  The workspace must hold BOTH copies (mi355q_op_flash_attn_ext_workspace reserves them) even where one side is f16 and is not copied:
+// conservative, and one condition for every pair.  k16 / v16: the descriptors the f16 rule is asked about (ws = the workspace, or any 256-byte aligned address for a question).
+static bool fa_mix_as_f16(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, float logit_softcap, void * ws, int has_workspace, size_t workspace_bytes,
+                          size_t * sc_bytes_out, mi355q_tensor * k16, mi355q_tensor * v16) {
+    size_t sc_bytes = 0;
+    if (!fa_kvq_as_f16(q, k, v, logit_softcap, has_workspace, workspace_bytes, &sc_bytes)) return false;
+    if ((k->type == 1 && !fa_al16(k)) || (v->type == 1 && !fa_al16(v))) return false;
+    const size_t kb16 = (size_t) k->ne[0] * k->ne[1] * k->ne[2] * k->ne[3] * 2;
+    char * kp = (char *) ws + sc_bytes, * vp = kp + ((kb16 + 255) & ~(size_t) 255);
+    auto as16 = [](const mi355q_tensor * t, char * p, mi355q_tensor & o) {
+        o = *t;
+        if (t->type != 1) { o.data = p; o.type = 1; o.nb[0] = 2; o.nb[1] = 2 * t->ne[0]; o.nb[2] = o.nb[1] * t->ne[1]; o.nb[3] = o.nb[2] * t->ne[2]; }
+    };
+    as16(k, kp, *k16); as16(v, vp, *v16);
+    if (sc_bytes_out) *sc_bytes_out = sc_bytes;
+    return true;
+}
+// The rule for a mixed pair; the shared checks of shapes and limits are behind it.
+static int fa_mix_path(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask, const mi355q_tensor * dst,
+                       float logit_softcap, int has_workspace, size_t workspace_bytes, uint32_t flags) {
+    const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1];
+    const bool kb = k->type != 1, vb = v->type != 1;
+    const int mode = fa_fused_mode();
+    if (DK % 32 || (vb && DV % 32)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: mixed K / V cache types need DK of whole 32-blocks, and DV too under a quantized V");
+    if ((kb && !fa_even(k)) || (vb && !fa_even(v))) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: mixed K / V cache types need even data and nb[1..3] of a quantized side");
+    // the fused kernel on the cache's own rows: asked for, not switched off, built for the pair and the buckets, aligned
+    const bool direct_ok = (flags & MI355Q_FA_KV_DIRECT) != 0 && mode != 0 && fattn_mfma_mix_built(k->type, v->type, DK, DV) && DV % 16 == 0 &&
+                           fa_al16(q) && (kb || fa_al16(k)) && (vb || fa_al16(v));
+    if (direct_ok && mode == 1 && (N >= 16 || n_kv > FA_KV_ROW_MAX)) return MI355Q_FA_PATH_FUSED_KV;                            // forced
+    mi355q_tensor k16, v16;
+    size_t sc_bytes = 0;
+    if (fa_mix_as_f16(q, k, v, logit_softcap, (void *) 256, has_workspace, workspace_bytes, &sc_bytes, &k16, &v16))            // a prompt with room for the copy: the f16 rule on it
+        return mi355q_op_flash_attn_ext_path2(q, &k16, &v16, mask, dst, logit_softcap, 1, sc_bytes, 0);
+    if (N >= 16 && direct_ok) return MI355Q_FA_PATH_FUSED_KV;                                                                   // a prompt without the copy
+    if (n_kv <= FA_KV_ROW_MAX) return MI355Q_FA_PATH_KV_ROW;                                                                    // the CPU's bits (k_flash_attn_ext_mix)
+    if (direct_ok) return MI355Q_FA_PATH_FUSED_KV;                                                                              // decode in the window the row kernel refuses
+    OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: mixed K / V cache types above 8192 positions need the f16 copy (>= 16 rows, no soft-cap, the workspace) or the "
+                                     "fused kernel: MI355Q_FA_KV_DIRECT, MI355Q_FA_FUSED not 0, f16 or q8_0 on one side, both head sizes in one of the buckets 64 / 128 / 256, "
+                                     "q and an f16 side 16-byte aligned");
+}
+
 int mi355q_op_flash_attn_ext_path(const mi355q_tensor * q, const mi355q_tensor * k, const mi355q_tensor * v, const mi355q_tensor * mask,
                                   const mi355q_tensor * dst, float logit_softcap, int has_workspace, size_t workspace_bytes) {
     return mi355q_op_flash_attn_ext_path2(q, k, v, mask, dst, logit_softcap, has_workspace, workspace_bytes, 0);
@@ -1384,14 +1399,28 @@ int mi355q_op_flash_attn_ext_path2(const mi355q_tensor * q, const mi355q_tensor 
     const bool kv_q80 = k->type == v->type && kv_block_bytes_rt(k->type) != 0;     // a quantized cache: both q8_0, q4_0, q4_1, q5_0, q5_1 or iq4_nl
     const bool kv_bf16 = k->type == MI355Q_T_BF16 && v->type == MI355Q_T_BF16;
     const int  kv_bb = kv_block_bytes_rt(k->type);
+    // flags & MI355Q_FA_KV_MIXED: K and V may differ in type, each of f16 or a block type; without the flag such a pair is refused as before
+    const bool kv_mix = (flags & MI355Q_FA_KV_MIXED) != 0 && k->type != v->type;
+    if (kv_mix) {
+        if ((k->type == MI355Q_T_BF16 && (fa_mix_side(v->type))) || (v->type == MI355Q_T_BF16 && fa_mix_side(k->type)))
+            OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: mixed K / V cache types with bf16 on one side are not built (f16, q8_0, q4_0, q4_1, q5_0, q5_1, iq4_nl)");
+        if (q->type != 0 || !fa_mix_side(k->type) || !fa_mix_side(v->type) || dst->type != 0 || (mask && mask->type != 1))
+            OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, mixed k / v each of f16 / q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl, mask f16, dst f32");
+    } else
     if (q->type != 0 || !((k->type == 1 && v->type == 1) || kv_q80 || kv_bf16) || dst->type != 0 || (mask && mask->type != 1)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: q f32, k / v both f16, both bf16 or both of one of q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl, mask f16, dst f32");
     const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
     if (q->ne[0] != DK || v->ne[1] != n_kv || k->ne[2] <= 0 || v->ne[2] <= 0 || n_head % k->ne[2] || n_head % v->ne[2] || k->ne[3] <= 0 || v->ne[3] <= 0 ||
         nb3 % k->ne[3] || nb3 % v->ne[3] || dst->ne[0] != DV || dst->ne[1] != n_head || dst->ne[2] != N || dst->ne[3] != nb3)
         OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: q [DK, N, H, B], k [DK, n_kv, Hk, Bk], v [DV, n_kv, Hv, Bv], dst [DV, H, N, B]");
-    if (q->nb[0] != 4 || k->nb[0] != (kv_q80 ? kv_bb : 2) || v->nb[0] != (kv_q80 ? kv_bb : 2) || dst->nb[0] != 4) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: innermost dimensions must be contiguous");
+    if (q->nb[0] != 4 || k->nb[0] != (kv_bb ? kv_bb : 2) || v->nb[0] != (kv_block_bytes_rt(v->type) ? kv_block_bytes_rt(v->type) : 2) || dst->nb[0] != 4) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: innermost dimensions must be contiguous");
     if (mask && (mask->ne[0] < n_kv || mask->ne[1] < N || mask->nb[0] != 2)) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: mask f16 [>= n_kv, >= N]");
     if (DK > 256 || DV > 256 || DK < 1 || DV < 1) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: head sizes up to 256");
+    if (kv_mix) {
+        if (N == 0 || n_head == 0 || nb3 == 0) return MI355Q_FA_PATH_KV_ROW;                                                   // (nothing to do)
+        if (n_kv == 0) OPS_FAIL(MI355Q_ERR_SHAPE, "op_flash_attn_ext: empty KV window");
+        if (n_head > 65535 || nb3 > 65535) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: too many heads / batches");
+        return fa_mix_path(q, k, v, mask, dst, logit_softcap, has_workspace, workspace_bytes, flags);
+    }
     const int mode = fa_fused_mode();
     // what the fused kernel takes: an f16 cache (or the f16 copy of a quantized one), head sizes of whole 16s, 16-byte aligned rows
     const bool as_f16 = kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, has_workspace, workspace_bytes, nullptr);
@@ -1452,7 +1481,8 @@ int mi355q_op_flash_attn_ext2(const mi355q_tensor * q, const mi355q_tensor * k, 
                               void * workspace, size_t workspace_bytes, void * stream, uint32_t flags) {
     const int path = mi355q_op_flash_attn_ext_path2(q, k, v, mask, dst, logit_softcap, workspace ? 1 : 0, workspace_bytes, flags);      // every check of types, shapes and limits
     if (path < 0) return path;
-    const bool kv_q80 = kv_block_bytes_rt(k->type) != 0, kv_bf16 = k->type == MI355Q_T_BF16;
+    const bool kv_mix = k->type != v->type;                   // (the path function has accepted the pair: MI355Q_FA_KV_MIXED)
+    const bool kv_q80 = !kv_mix && kv_block_bytes_rt(k->type) != 0, kv_bf16 = k->type == MI355Q_T_BF16;
     const int64_t DK = k->ne[0], DV = v->ne[0], n_kv = k->ne[1], N = q->ne[1], n_head = q->ne[2], nb3 = q->ne[3];
     if (N == 0 || n_head == 0 || nb3 == 0) return MI355Q_OK;
     if (logit_softcap != 0.0f) scale /= logit_softcap;                          // ops.cpp:6757-6759
@@ -1460,6 +1490,32 @@ int mi355q_op_flash_attn_ext2(const mi355q_tensor * q, const mi355q_tensor * k, 
     const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
     mi355q_tensor k16, v16;                                   // (a quantized cache under a prefill batch: its f16 copy)
     size_t sc_bytes = 0;
+    if (kv_mix) {
+        if (path == MI355Q_FA_PATH_KV_ROW) {                  // the CPU's arithmetic, the scores by K's type and the accumulator by V's (k_flash_attn_ext_mix)
+            if (fattn_mix_launch(q, k, v, mask, dst, scale, max_bias, logit_softcap, m0, m1, n_head_log2, stream) != MI355Q_OK) OPS_FAIL(MI355Q_ERR_HIP, "op_flash_attn_ext: mixed-cache row kernel launch failed");
+            return MI355Q_OK;
+        }
+        if (path != MI355Q_FA_PATH_FUSED_KV) {                // every other answer is the f16 rule's about the copy: decode each block side with its own type
+            if (!fa_mix_as_f16(q, k, v, logit_softcap, workspace, workspace ? 1 : 0, workspace_bytes, &sc_bytes, &k16, &v16)) OPS_FAIL(MI355Q_ERR_UNSUPPORTED, "op_flash_attn_ext: mixed cache: no f16 copy for this call");
+            for (int side = 0; side < 2; ++side) {
+                const mi355q_tensor * t = side ? v : k;
+                if (t->type == 1) continue;
+                __half * out = (__half *) (side ? v16.data : k16.data);
+                const int64_t n = t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3];
+#define DEQ_MIX(T) hipLaunchKernelGGL(k_dequant_cache_f16<T>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t) stream, to_d(t), out)
+                switch (t->type) {
+                    case MI355Q_TYPE_Q8_0:   DEQ_MIX(MI355Q_TYPE_Q8_0); break;
+                    case MI355Q_TYPE_Q4_0:   DEQ_MIX(MI355Q_TYPE_Q4_0); break;
+                    case MI355Q_TYPE_Q4_1:   DEQ_MIX(MI355Q_TYPE_Q4_1); break;
+                    case MI355Q_TYPE_Q5_0:   DEQ_MIX(MI355Q_TYPE_Q5_0); break;
+                    case MI355Q_TYPE_Q5_1:   DEQ_MIX(MI355Q_TYPE_Q5_1); break;
+                    default:                 DEQ_MIX(MI355Q_TYPE_IQ4_NL); break;
+                }
+#undef DEQ_MIX
+            }
+            return mi355q_op_flash_attn_ext(q, &k16, &v16, mask, dst, logit_softcap != 0.0f ? scale * logit_softcap : scale, max_bias, logit_softcap, workspace, sc_bytes, stream);
+        }
+    }
     if (path != MI355Q_FA_PATH_FUSED_KV && kv_q80 && fa_kvq_as_f16(q, k, v, logit_softcap, workspace ? 1 : 0, workspace_bytes, &sc_bytes)) {
         // Many query rows: one workgroup per row re-streams (and re-decodes) the cache for every row.  The cache is decoded ONCE into scratch as f16 and the
         // matrix-core paths below take it (q in f16 against the dequantized K instead of the CPU's Q8_0-quantized q: ~1e-3 of a score, NMSE 1e-6 of the

@@ -67,6 +67,7 @@ FA_PATH_ROW_SEQ, FA_PATH_ROW_F32, FA_PATH_ROW_SPLIT, FA_PATH_KV_ROW, FA_PATH_MFM
 FA_PATH_NAMES = {FA_PATH_ROW_SEQ: "row_seq", FA_PATH_ROW_F32: "row_f32", FA_PATH_ROW_SPLIT: "row_split", FA_PATH_KV_ROW: "kv_row",
                  FA_PATH_MFMA3: "mfma3", FA_PATH_FUSED: "fused", FA_PATH_FUSED_KV: "fused_kv"}
 FA_KV_DIRECT = 0x1      # MI355Q_FA_KV_DIRECT: the fused kernel may read a quantized or bf16 cache's own rows (the ...2 entry points)
+FA_KV_MIXED = 0x2       # MI355Q_FA_KV_MIXED: k and v may differ in type, each of f16 or a block type (the ...2 entry points)
 ERR_UNSUPPORTED, ERR_SHAPE = -1, -2
 
 
@@ -523,22 +524,29 @@ def op_unary_mul(uop: int, a, b):
     return out
 
 
+def _fa_flags(kv_direct: bool, kv_mixed: bool) -> int:
+    return (FA_KV_DIRECT if kv_direct else 0) | (FA_KV_MIXED if kv_mixed else 0)
+
+
 def op_flash_attn_ext(q, k, v, mask, scale: float, max_bias: float = 0.0, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0",
-                      kv_direct: bool = False):
+                      kv_direct: bool = False, kv_v=None, kv_mixed: bool = False):
     """GGML_OP_FLASH_ATTN_EXT: q f32 [B, H, N, DK] (torch order), k f16 [Bk, Hk, n_kv, DK], v f16 [Bv, Hv, n_kv, DV], mask f16 [>= N, >= n_kv]
     or None -> f32 [B, N, H, DV].  k / v may both be bf16 (a bf16 cache) or uint8 block rows (`kv`: a q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl cache).
-    `kv_direct`: mi355q_op_flash_attn_ext2 with MI355Q_FA_KV_DIRECT -- the fused kernel may read such a cache's own rows."""
+    `kv_direct`: mi355q_op_flash_attn_ext2 with MI355Q_FA_KV_DIRECT -- the fused kernel may read such a cache's own rows.
+    `kv_mixed`: ... with MI355Q_FA_KV_MIXED -- k and v may differ in type: each an f16 tensor or uint8 block rows, `kv` the block type of k and
+    `kv_v` the one of v where it differs (None: `kv`)."""
     torch = _torch()
-    out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3]), dtype=torch.float32, device=q.device)
+    kv_v = kv if kv_v is None else kv_v
+    tdk = (lambda t: _td_q8_0(t, kv)) if k.dtype == torch.uint8 else _td       # (uint8: block_q8_0 / block_q4_0 rows, a quantized cache)
+    tdv = (lambda t: _td_q8_0(t, kv_v)) if v.dtype == torch.uint8 else _td
+    dv = v.shape[3] // KV_BLOCK[kv_v][0] * 32 if v.dtype == torch.uint8 else v.shape[3]
+    out = torch.empty((q.shape[0], q.shape[2], q.shape[1], dv), dtype=torch.float32, device=q.device)
     ws, wsb = (_workspace(torch, int(lib().mi355q_op_flash_attn_ext_workspace(v.shape[3], q.shape[2], q.shape[1], q.shape[0], k.shape[2])), q.device)
                if split else (None, 0))
-    tdkv = (lambda t: _td_q8_0(t, kv)) if k.dtype == torch.uint8 else _td      # (uint8: block_q8_0 / block_q4_0 rows, a quantized cache)
-    if k.dtype == torch.uint8:
-        out = torch.empty((q.shape[0], q.shape[2], q.shape[1], v.shape[3] // KV_BLOCK[kv][0] * 32), dtype=torch.float32, device=q.device)
-    args = (C.byref(_td(q)), C.byref(tdkv(k)), C.byref(tdkv(v)), C.byref(_td(mask)) if mask is not None else None,
+    args = (C.byref(_td(q)), C.byref(tdk(k)), C.byref(tdv(v)), C.byref(_td(mask)) if mask is not None else None,
             C.byref(_td(out)), scale, max_bias, logit_softcap, ws.data_ptr() if ws is not None else None, wsb, _stream(torch))
-    if kv_direct:
-        _check(lib().mi355q_op_flash_attn_ext2(*args, FA_KV_DIRECT), "op_flash_attn_ext2")
+    if kv_direct or kv_mixed:
+        _check(lib().mi355q_op_flash_attn_ext2(*args, _fa_flags(kv_direct, kv_mixed)), "op_flash_attn_ext2")
     else:
         _check(lib().mi355q_op_flash_attn_ext(*args), "op_flash_attn_ext")
     return out
@@ -561,23 +569,24 @@ def tensor_desc(type_code: int, ne, nb=None, data: int = 0x10000) -> _Tensor:
 
 
 def op_flash_attn_ext_path(q, k, v, mask=None, logit_softcap: float = 0.0, split: bool = True, kv: str = "q8_0", workspace_bytes=None,
-                           kv_direct: bool = False) -> int:
+                           kv_direct: bool = False, kv_v=None, kv_mixed: bool = False) -> int:
     """Which kernels op_flash_attn_ext would run for these operands: one of FA_PATH_*, or the negative error code the call would return
     (last_error() has the message).  No device work.  Operands are torch tensors as for op_flash_attn_ext, or descriptors from tensor_desc.
     `split` = a workspace is passed (of `workspace_bytes`, by default what mi355q_op_flash_attn_ext_workspace asks for).
-    `kv_direct`: ask mi355q_op_flash_attn_ext_path2 with MI355Q_FA_KV_DIRECT, as op_flash_attn_ext(kv_direct=True) does."""
-    def desc(t):
+    `kv_direct`: ask mi355q_op_flash_attn_ext_path2 with MI355Q_FA_KV_DIRECT, as op_flash_attn_ext(kv_direct=True) does.
+    `kv_mixed` / `kv_v`: ... with MI355Q_FA_KV_MIXED; `kv_v` is v's block type where it differs from `kv`."""
+    def desc(t, kvt=kv):
         if t is None or isinstance(t, _Tensor):
             return t
-        return _td_q8_0(t, kv) if t.dtype == _torch().uint8 else _td(t)
-    dq, dk, dv, dm = desc(q), desc(k), desc(v), desc(mask)
+        return _td_q8_0(t, kvt) if t.dtype == _torch().uint8 else _td(t)
+    dq, dk, dv, dm = desc(q), desc(k), desc(v, kv if kv_v is None else kv_v), desc(mask)
     out = tensor_desc(0, [dv.ne[0], dq.ne[2], dq.ne[1], dq.ne[3]])
     if workspace_bytes is None:
         workspace_bytes = int(lib().mi355q_op_flash_attn_ext_workspace(dv.ne[0], dq.ne[1], dq.ne[2], dq.ne[3], dk.ne[1])) if split else 0
     args = (C.byref(dq), C.byref(dk), C.byref(dv), C.byref(dm) if dm is not None else None, C.byref(out),
             logit_softcap, 1 if split and workspace_bytes > 0 else 0, workspace_bytes)
-    if kv_direct:
-        return int(lib().mi355q_op_flash_attn_ext_path2(*args, FA_KV_DIRECT))
+    if kv_direct or kv_mixed:
+        return int(lib().mi355q_op_flash_attn_ext_path2(*args, _fa_flags(kv_direct, kv_mixed)))
     return int(lib().mi355q_op_flash_attn_ext_path(*args))
 
 
