@@ -231,6 +231,28 @@ int    mi355q_mul_mat_id(int type, const void *w, int64_t w_stride_bytes, int64_
 #define MI355Q_STAGE_KV_Q5_0   0x20
 #define MI355Q_STAGE_KV_Q5_1   0x40
 #define MI355Q_STAGE_KV_IQ4_NL 0x80
+/* ATTN stages over MIXED K / V cache types (-ctk A -ctv B): a MI355Q_STAGE_KVV_* bit names V's type (at most one bit), and
+ * the MI355Q_STAGE_KV_* bits above then name K's type alone (no bit: f16).  Without a KVV bit the KV bits keep their meaning: K and V both have
+ * that type.  A KVV bit equal to K's type is the same-type stage, with the same bits.  Each side keeps its own layout: a block side as above
+ * (cache + j*nb_pos + g*nb_head + b*BB, even addresses and strides, head_dim % 32 == 0, this token's row stored as mi355q_op_cpy f32 -> the
+ * side's type stores it), an f16 side as the f16 stage has it (rows per position, v_nb_dim = 2; this token's row rounded to f16, V through
+ * v_dst_nb).  Only the flash layout.  The scores follow K's type (q to its vec_dot_type, its vec_dot), the accumulator V's (f16: the F16
+ * accumulator; a block type: F32 over its to_float).  One split per head: the output is mi355q_op_flash_attn_ext2's with MI355Q_FA_KV_MIXED on
+ * the same cache, bit for bit.  Several splits: a block V merges per-split F32 accumulators as the same-type stages do; an f16 V is not merged --
+ * its splits score in parallel and then continue ONE F16-accumulator walk, split after split, which is the single walk bit for bit.  plan_create refuses a window whose
+ * per-split rows of both sides do not fit the LDS (the message names the pair and its limit), the transposed V layout, head sizes that are not
+ * whole blocks, odd addresses or strides on a block side, and the ring engine (MI355Q_PLAN_ENGINE=ring); there is no bit for bf16.
+ * The bits were added without a change of MI355Q_API_VERSION (no function or structure changed): a library older than them does not know
+ * them and reads such a stage as a same-type cache of K's type.  A caller that may meet an older library probes once: mi355q_plan_create
+ * of an ATTN stage with two KVV bits set fails with MI355Q_ERR_UNSUPPORTED in a library that knows them (nothing is launched) and not in one
+ * that does not.                                                                                                                               */
+#define MI355Q_STAGE_KVV_F16    0x100
+#define MI355Q_STAGE_KVV_Q8_0   0x200
+#define MI355Q_STAGE_KVV_Q4_0   0x400
+#define MI355Q_STAGE_KVV_Q4_1   0x800
+#define MI355Q_STAGE_KVV_Q5_0   0x1000
+#define MI355Q_STAGE_KVV_Q5_1   0x2000
+#define MI355Q_STAGE_KVV_IQ4_NL 0x4000
 #define MI355Q_STAGE_GEMV 0
 #define MI355Q_STAGE_ATTN 1
 #define MI355Q_X_PLAIN     0

@@ -126,10 +126,14 @@ struct mi355_plan_matcher {
         }
         if (max_bias != 0.0f || softcap != 0.0f) return false;
         // the cache: f16, or (flash graphs only) both K and V in blocks of one of Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL (-ctk T -ctv T): the stage flag MI355Q_STAGE_KV_*
-        const enum ggml_type kvt = kview->type;
-        const bool kv_quant = fa && mi355_kv_block_type(kvt);
-        const size_t kv_nb0 = kv_quant ? ggml_type_size(kvt) : 2;                              // bytes per element (f16) or per 32-block
-        if ((kvt != GGML_TYPE_F16 && !kv_quant) || vview->type != kvt || !kview->view_src || !vview->view_src || kview->nb[0] != kv_nb0) return false;
+        // Mixed types (-ctk A -ctv B, each of f16 or a block type; flash graphs only): K's type keeps the MI355Q_STAGE_KV_* bit and a MI355Q_STAGE_KVV_* bit names
+        // V's -- only with MI355_PLAN_KV_MIXED=1 in the environment (off by default: DESIGN.md 5.6); otherwise such a graph runs node by node.
+        const enum ggml_type kvt = kview->type, vvt = vview->type;
+        const bool kv_quant = fa && mi355_kv_block_type(kvt), v_quant = fa && mi355_kv_block_type(vvt);
+        const bool kv_mixed = vvt != kvt;
+        if (kv_mixed) { const char * e = getenv("MI355_PLAN_KV_MIXED"); if (!fa || !e || atoi(e) != 1) return false; }
+        const size_t kv_nb0 = kv_quant ? ggml_type_size(kvt) : 2, v_nb0 = v_quant ? ggml_type_size(vvt) : 2;     // bytes per element (f16) or per 32-block, per side
+        if ((kvt != GGML_TYPE_F16 && !kv_quant) || (vvt != GGML_TYPE_F16 && !v_quant) || !kview->view_src || !vview->view_src || kview->nb[0] != kv_nb0) return false;
         const struct ggml_tensor * rq = mi355_skip_views(qperm);
         if (!rq || rq->op != GGML_OP_ROPE) return false;
         const struct ggml_tensor * qm = mat_behind(rq->src[0]);
@@ -146,8 +150,8 @@ struct mi355_plan_matcher {
             if (n->src[1]->view_src == kview->view_src) { if (ck) return false; ck = n; }
             else if (n->src[1]->view_src == vview->view_src) { if (cv) return false; cv = n; }
         }
-        if (!ck || !cv || ck->src[1]->type != kvt || cv->src[1]->type != kvt) return false;
-        if (kv_quant && (ck->src[0]->type != GGML_TYPE_F32 || cv->src[0]->type != GGML_TYPE_F32)) return false;       // CPY f32 -> the cache type
+        if (!ck || !cv || ck->src[1]->type != kvt || cv->src[1]->type != vvt) return false;                            // each store's destination has its own side's type
+        if ((kv_quant && ck->src[0]->type != GGML_TYPE_F32) || (v_quant && cv->src[0]->type != GGML_TYPE_F32)) return false;       // CPY f32 -> the cache type
         const struct ggml_tensor * rk = mi355_skip_views(ck->src[0]);
         if (!rk || rk->op != GGML_OP_ROPE || rk->src[1] != rq->src[1] || rk->src[2] != rq->src[2]) return false;
         if (memcmp(rk->op_params, rq->op_params, sizeof(rk->op_params)) != 0) return false;
@@ -180,7 +184,7 @@ struct mi355_plan_matcher {
         a->freq_factors = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
         a->k_cache = kview->data; a->k_nb_pos = (int64_t) kview->nb[1]; a->k_nb_head = (int64_t) kview->nb[2];
         a->v_cache = vview->data;
-        if (fa) { if (vview->nb[0] != kv_nb0 || vview->ne[0] != hd || vview->ne[1] != n_kv) return false; a->v_nb_dim = (int64_t) kv_nb0; a->v_nb_pos = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
+        if (fa) { if (vview->nb[0] != v_nb0 || vview->ne[0] != hd || vview->ne[1] != n_kv) return false; a->v_nb_dim = (int64_t) v_nb0; a->v_nb_pos = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
         else    { if (vview->nb[0] != 2 || vview->ne[0] != n_kv || vview->ne[1] != hd) return false; a->v_nb_pos = 2; a->v_nb_dim = (int64_t) vview->nb[1]; a->v_nb_head = (int64_t) vview->nb[2]; }
         a->k_dst = (void * const *) (dest_table + cpy_ordinal[(size_t) idx(ck)]);
         a->v_dst = (void * const *) (dest_table + cpy_ordinal[(size_t) idx(cv)]);
@@ -188,7 +192,7 @@ struct mi355_plan_matcher {
         const struct ggml_tensor * vd = cv->src[1];
         a->v_dst_nb = vd->ne[0] == 1 ? (int64_t) vd->nb[1] : (int64_t) vd->nb[0];
         if (vd->ne[0] != 1 && !ggml_is_contiguous(vd)) return false;
-        if (kv_quant && (vd->ne[0] == 1 || vd->nb[0] != kv_nb0)) return false;                   // (a quantized V row is stored contiguously too)
+        if (v_quant && (vd->ne[0] == 1 || vd->nb[0] != v_nb0)) return false;                   // (a quantized V row is stored contiguously too)
         a->mask = mask ? mask->data : nullptr; a->mask_f16 = mask && mask->type == GGML_TYPE_F16;
         if (mask_cast) mask_casts.insert(mask_cast);
         a->n_head = (int) n_head; a->n_head_kv = (int) n_head_kv; a->head_dim = (int) hd; a->n_kv = (int) n_kv;
@@ -196,16 +200,19 @@ struct mi355_plan_matcher {
         a->out = (float *) top->data;
         if (kview->view_src->buffer == nullptr || !mi355_buft_is_ours(kview->view_src->buffer->buft) || !mi355_buft_is_ours(vview->view_src->buffer->buft)) return false;
 
+        const std::string kv_name = kv_mixed ? std::string(ggml_type_name(kvt)) + " / " + ggml_type_name(vvt) : std::string(ggml_type_name(kvt));     // `kv q8_0`, or `kv q8_0 / q4_0` for a mixed cache
         if (getenv("MI355_PLAN_DEBUG"))
             fprintf(stderr, "MI355 plan attn: q %p k %p v %p pos %p | n_head %d n_head_kv %d hd %d n_kv %d | rope n_dims %d mode %d base %g | kv %s | k_cache %p nb_pos %lld nb_head %lld | v_cache %p nb_pos %lld nb_dim %lld nb_head %lld | "
                             "cpy slots k %d v %d (k dst now %p, v dst now %p) v_dst_nb %lld | mask %p f16 %d scale %g | out %p\n",
-                    (void *) a->q, (void *) a->k, (void *) a->v, (void *) a->pos, a->n_head, a->n_head_kv, a->head_dim, a->n_kv, a->rope.n_dims, a->rope.mode, a->rope.freq_base, ggml_type_name(kvt),
+                    (void *) a->q, (void *) a->k, (void *) a->v, (void *) a->pos, a->n_head, a->n_head_kv, a->head_dim, a->n_kv, a->rope.n_dims, a->rope.mode, a->rope.freq_base, kv_name.c_str(),
                     a->k_cache, (long long) a->k_nb_pos, (long long) a->k_nb_head, a->v_cache, (long long) a->v_nb_pos, (long long) a->v_nb_dim, (long long) a->v_nb_head,
                     cpy_ordinal[(size_t) idx(ck)], cpy_ordinal[(size_t) idx(cv)], ck->data, cv->data, (long long) a->v_dst_nb, a->mask, a->mask_f16, a->scale, (void *) a->out);
         mi355q_stage st; memset(&st, 0, sizeof(st));
         st.kind = MI355Q_STAGE_ATTN; st.attn = a; st.flags = MI355Q_STAGE_NO_PLAIN;
         if (kv_quant) st.flags |= kvt == GGML_TYPE_Q8_0 ? MI355Q_STAGE_KV_Q8_0 : kvt == GGML_TYPE_Q4_0 ? MI355Q_STAGE_KV_Q4_0 : kvt == GGML_TYPE_Q4_1 ? MI355Q_STAGE_KV_Q4_1 :
                                   kvt == GGML_TYPE_Q5_0 ? MI355Q_STAGE_KV_Q5_0 : kvt == GGML_TYPE_Q5_1 ? MI355Q_STAGE_KV_Q5_1 : MI355Q_STAGE_KV_IQ4_NL;
+        if (kv_mixed) st.flags |= vvt == GGML_TYPE_F16 ? MI355Q_STAGE_KVV_F16 : vvt == GGML_TYPE_Q8_0 ? MI355Q_STAGE_KVV_Q8_0 : vvt == GGML_TYPE_Q4_0 ? MI355Q_STAGE_KVV_Q4_0 : vvt == GGML_TYPE_Q4_1 ? MI355Q_STAGE_KVV_Q4_1 :
+                                  vvt == GGML_TYPE_Q5_0 ? MI355Q_STAGE_KVV_Q5_0 : vvt == GGML_TYPE_Q5_1 ? MI355Q_STAGE_KVV_Q5_1 : MI355Q_STAGE_KVV_IQ4_NL;
         b.stages.push_back(st);
         b.anchor.push_back(idx(fa ? fa : kq));
         b.outs.push_back({ top });

@@ -273,8 +273,8 @@ __device__ __forceinline__ float kv_dequant_elem(const char * blk, int e) {
 // ---- the online softmax in position order, by ONE wave (all 64 lanes): scores s[0, n) (-inf = skipped) -> s[j] = the weight vs of position j,
 // msv[j] = the accumulator's rescale factor ms (a new maximum: ms = expf(Mprev - s), vs = 1; otherwise ms = 1, vs = expf(s - Mprev); skipped:
 // ms = 1, vs = 0).  Returns the final maximum (uniform; -inf when every position is skipped).  tab: PLAN_EXP2F_T[lane & 31].
-__device__ __forceinline__ float fa_seq_weights(float * s, float * msv, int64_t n, int lane, unsigned long long tab) {
-    float carry = -INFINITY;
+__device__ __forceinline__ float fa_seq_weights(float * s, float * msv, int64_t n, int lane, unsigned long long tab, float carry0 = -INFINITY) {
+    float carry = carry0;                                                       // (the maximum a walk over earlier positions ended with: the decode plan's chained splits)
     for (int64_t j0 = 0; j0 < n; j0 += 64) {
         const int64_t j = j0 + lane;
         const float sj = j < n ? s[j] : -INFINITY;

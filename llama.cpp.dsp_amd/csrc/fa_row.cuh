@@ -43,9 +43,11 @@ __device__ __forceinline__ float fa_dot_f16_seq(const float (&kr)[4], const floa
 }
 
 // ---- V . P for one output element of an f16 V with the CPU's F16 accumulator (VKQ16): vb = the element at position 0, nb_pos = bytes between positions,
-// ws / msv = fa_seq_weights' weights and rescale factors.  acc is an f16 value at all times; skipped positions are never read.
-__device__ __forceinline__ void fa_pv_f16_seq(const char * vb, int64_t nb_pos, const float * ws, const float * msv, int64_t n, float & acc_out, float & S_out) {
-    float acc = 0.0f, S = 0.0f;
+// ws / msv = fa_seq_weights' weights and rescale factors.  acc is an f16 value at all times; skipped positions are never read.  acc0 / S0: where a walk
+// over earlier positions ended (the decode plan's chained splits, plan.hip plan_attn_mix step 3b); 0 for a walk from the start.
+__device__ __forceinline__ void fa_pv_f16_seq(const char * vb, int64_t nb_pos, const float * ws, const float * msv, int64_t n, float & acc_out, float & S_out,
+                                              float acc0 = 0.0f, float S0 = 0.0f) {
+    float acc = acc0, S = S0;
 #pragma unroll 4
     for (int64_t j = 0; j < n; ++j) {
         const float vs = ws[j], ms = msv[j];

@@ -33,6 +33,7 @@
 
 #include "gemv_stream.cuh"
 #include "fa_quant.cuh"
+#include "fa_row.cuh"
 
 namespace mi355q {
 
@@ -42,7 +43,7 @@ __host__ __device__ constexpr int plan_depth(int type) {   // Q5_K / Q6_K slots 
     // than Q4_K's 1152 bytes in 8, so the full depth, which is still fewer bytes in flight than Q4_K's
     return (type == MI355Q_TYPE_Q5_K || type == MI355Q_TYPE_Q6_K) ? 6 : PLAN_D_MAX;
 }
-enum { PLAN_F_NEW_X = 2, PLAN_F_PLAIN_Y = 4, PLAN_F_SUM = 8, PLAN_F_SUM_PLAIN = 16, PLAN_F_PAIRED = 32, PLAN_F_DIRECT = 64, PLAN_F_ATTN_LDS = 128, PLAN_F_ATTN_Q = 256 };
+enum { PLAN_F_NEW_X = 2, PLAN_F_PLAIN_Y = 4, PLAN_F_SUM = 8, PLAN_F_SUM_PLAIN = 16, PLAN_F_PAIRED = 32, PLAN_F_DIRECT = 64, PLAN_F_ATTN_LDS = 128, PLAN_F_ATTN_Q = 256, PLAN_F_ATTN_MIX = 512 };
 enum { PLAN_K_GEMV = 0, PLAN_K_ATTN = 1, PLAN_K_COMBINE = 2 };
 enum { PLAN_SYNC_ABORT = 0, PLAN_SYNC_WORDS = 32 };
 
@@ -66,6 +67,7 @@ struct AttnStage {
     int fa_seq;                                    // rows-per-position V cache, window in one workgroup: the CPU's sequential f16 accumulation (plan_attn_lds)
     int entry_barrier;                             // the previous stage is not a GEMV: its last LDS reads must be fenced off
     int kv_type, kv_rb, kv_unit;                   // quantized cache (plan_attn_q80): MI355Q_TYPE_Q8_0 / _Q4_0 / _Q4_1 / _Q5_0 / _Q5_1 / _IQ4_NL (0: f16), bytes per head row, bytes per copy unit (2, 4, 8)
+    int mixed, v_type, v_rb, v_unit, chain;             // mixed K / V cache types (plan_attn_mix): kv_type / kv_rb / kv_unit describe K's side, these V's; a type is a block type or 1 (f16: rb = 2 hd); units 2, 4, 8; chain: an f16 V over several splits, walked split after split (no merge stage)
     float scale;
     // rope (ggml_rope_cache_init; see ops_glue.hip k_rope)
     int n_dims, neox; float freq_scale, ext_factor, attn_factor, theta_scale, corr0, corr1;
@@ -1506,6 +1508,310 @@ static __device__ __noinline__ bool plan_attn_q80(AttnC a_in, const StageCtx & c
     return true;
 }
 
+// ---- attention of one token over MIXED K / V cache types (-ctk A -ctv B, each of f16, Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL), K / V window in LDS ----------------------
+// plan_attn_q80's phases with the K phases taken by K's type and the V phases by V's: the CPU's arithmetic is separable by side (DESIGN.md 5.7g;
+// fattn_mix.hip k_flash_attn_ext_mix is the node op with the same pieces).  The flash layout only.  The body below runs the phases; what a side
+// does in a phase is a helper templated on that side's type alone (1 = f16), reached through a switch on the stage's K type or V type:
+//   K side   this token's row -> the window and the cache (mix_store_row);  the scores (mix_scores): a block K against q quantized to its
+//            vec_dot_type, one position per thread (fa_quantize_q, fa_dot_q80); an f16 K against q rounded to f16, one position per wave in
+//            ggml_vec_dot_f16's order (fa_dot_f16_seq, fa_row.cuh)
+//   V side   this token's row (mix_store_row);  V . P, one thread per output dim (mix_pv): a block V dequantized into the F32 accumulator
+//            (fa_pv_q80); an f16 V into the F16 accumulator (fa_pv_f16_seq's walk), which over several splits is CHAINED: split sp continues
+//            the walk of split sp - 1 (step 3b), because no merge of per-split sums reproduces the CPU's F16 rounding chain
+// The window copy depends on a side's row bytes and widest aligned unit only.  One split: the output is k_flash_attn_ext_mix's, bit for bit.
+// Several, a block V: each split publishes (its F32 accumulator, its maximum, its sum S) and plan_attn_combine merges them, as for the same-type stages.
+// Several, an f16 V: the chain's last split publishes the single walk's result, bit for bit; there is no merge stage.
+__device__ __forceinline__ void mix_copy_rows(char * lds_dst, const char * src, int64_t nb, int rows, int rb, int unit, int wi, int n_w, int lane) {
+    if (unit == 8)      plan_copy_rows<uint2>(lds_dst, src, nb, rows, rb, wi, n_w, lane);
+    else if (unit == 4) plan_copy_rows<uint32_t>(lds_dst, src, nb, rows, rb, wi, n_w, lane);
+    else                plan_copy_rows<uint16_t>(lds_dst, src, nb, rows, rb, wi, n_w, lane);
+}
+
+// this token's row of one side, by ONE wave (all 64 lanes): x[hd] f32 -> the side's type, into the window row `win` and the cache row `dst` (either may be
+// null).  A block type: CPY f32 -> T's blocks, contiguous.  f16: rounded as the f16 stage stores it, element e at dst + e * dst_nb.
+template <int T>
+__device__ __forceinline__ void mix_store_row(const float * x, int hd, int lane, char * win, char * dst, int64_t dst_nb) {
+    if constexpr (T == 1) {
+        for (int e = lane; e < hd; e += 64) {
+            const __half hv = __float2half_rn(x[e]);
+            if (win) ((__half *) win)[e] = hv;
+            if (dst) *(__half *) (dst + (int64_t) e * dst_nb) = hv;
+        }
+    } else {
+        const int e = 4 * lane;
+        const float4 v4 = e < hd ? make_float4(x[e], x[e + 1], x[e + 2], x[e + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        KvBlk o;
+        kv_quant_group8<T>(v4, o);
+        if (e < hd) {
+            const int off = kv_block_bytes<T>() * (lane >> 3), l8 = lane & 7;
+            if (win) kv_store_group8<T>(win + off, l8, o);
+            if (dst) kv_store_group8<T>(dst + off, l8, o);
+        }
+    }
+}
+__device__ __forceinline__ void mix_store_row_rt(int type, const float * x, int hd, int lane, char * win, char * dst, int64_t dst_nb) {
+    switch (type) {                                                            // (uniform)
+    case 1:                  mix_store_row<1>(x, hd, lane, win, dst, dst_nb); break;
+    case MI355Q_TYPE_Q8_0:   mix_store_row<MI355Q_TYPE_Q8_0>(x, hd, lane, win, dst, dst_nb); break;
+    case MI355Q_TYPE_Q4_0:   mix_store_row<MI355Q_TYPE_Q4_0>(x, hd, lane, win, dst, dst_nb); break;
+    case MI355Q_TYPE_Q4_1:   mix_store_row<MI355Q_TYPE_Q4_1>(x, hd, lane, win, dst, dst_nb); break;
+    case MI355Q_TYPE_Q5_0:   mix_store_row<MI355Q_TYPE_Q5_0>(x, hd, lane, win, dst, dst_nb); break;
+    case MI355Q_TYPE_Q5_1:   mix_store_row<MI355Q_TYPE_Q5_1>(x, hd, lane, win, dst, dst_nb); break;
+    default:                 mix_store_row<MI355Q_TYPE_IQ4_NL>(x, hd, lane, win, dst, dst_nb); break;
+    }
+}
+
+// the scores of the split's cnt positions: sc[jj] = mask -> s * scale + mask (a masked position stays -inf whatever its row holds)
+template <int KT>
+__device__ __forceinline__ void mix_scores(const char * kwin, int rb, int cnt, int hd, const float * sq, const float * qd, const uint32_t * qq, const float * qsum,
+                                           float scale, float * sc, int tid, int wave, int lane) {
+    const int nblk = hd >> 5;
+    if constexpr (KT == 1) {
+        float qh[4];                                                           // q rounded to f16, element lane + 64 u
+#pragma unroll
+        for (int u = 0; u < 4; ++u) qh[u] = lane + 64 * u < hd ? __half2float(__float2half_rn(sq[lane + 64 * u])) : 0.0f;
+        for (int jj = wave; jj < cnt; jj += GEMV_WAVES) {                       // one position per wave
+            const float m = sc[jj];
+            if (m == -INFINITY) continue;                                      // (uniform)
+            const __half * kp = (const __half *) (kwin + (size_t) jj * rb);
+            float kr[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) kr[u] = lane + 64 * u < hd ? __half2float(kp[lane + 64 * u]) : 0.0f;
+            const float s = fa_dot_f16_seq(kr, qh, nblk, lane);
+            if (lane == 0) sc[jj] = __fadd_rn(__fmul_rn(s, scale), m);
+        }
+    } else {
+        for (int jj = tid; jj < cnt; jj += GEMV_THREADS) {                      // one position per thread
+            const float m = sc[jj];
+            sc[jj] = m == -INFINITY ? -INFINITY : __fadd_rn(__fmul_rn(fa_dot_q80<KT>(kwin + (size_t) jj * rb, qd, qq, nblk, qsum), scale), m);
+        }
+    }
+}
+
+template <int VT>
+__device__ __forceinline__ void mix_pv(const char * vwin, int rb, int e, const float * sc, const float * msv, int cnt, float acc0, float S0, float & acc, float & S) {
+    if constexpr (VT == 1) fa_pv_f16_seq(vwin + 2 * e, rb, sc, msv, cnt, acc, S, acc0, S0);      /* (a chained split continues the walk of the one before) */
+    else fa_pv_q80<VT>(vwin + kv_block_bytes<VT>() * (e >> 5), rb, e & 31, sc, msv, cnt, acc, S);
+}
+
+static __device__ __noinline__ bool plan_attn_mix(AttnC a_in, const StageCtx & c_in, unsigned tag_in) {
+    const AttnC a = (AttnC) (uintptr_t) uniform_ptr((const void *) (uintptr_t) a_in);
+    extern __shared__ __attribute__((aligned(16))) uint8_t plan_lds_attnm[];
+    StageCtx c;
+    c.image = __builtin_amdgcn_readfirstlane(c_in.image);
+    c.lds = plan_lds_attnm; c.ctl = (int *) (plan_lds_attnm + c.image); c.part = (double *) (plan_lds_attnm + c.image + 64);
+    c.stg = (float *) (plan_lds_attnm + c.image + 64 + 8 * GEMV_WAVES + 1024);
+    c.sync = uniform_ptr(c_in.sync); c.timeout = c_in.timeout;
+    c.grid = (unsigned) __builtin_amdgcn_readfirstlane((int) c_in.grid); c.epoch = (unsigned) __builtin_amdgcn_readfirstlane((int) c_in.epoch);
+    c.even = c_in.even; c.stage = __builtin_amdgcn_readfirstlane(c_in.stage);
+    c.next_desc = uniform_ptr(c_in.next_desc); c.next_attn = uniform_ptr(c_in.next_attn); c.next_desc2 = uniform_ptr(c_in.next_desc2); c.pre_lds = c_in.pre_lds;
+    const unsigned tag = (unsigned) __builtin_amdgcn_readfirstlane((int) tag_in);
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int tid = (int) threadIdx.x;
+    const int hd = a->hd, n_split = a->n_split;
+    if ((int) blockIdx.x >= a->n_head * n_split) return true;                    // (uniform)
+    const int h = (int) blockIdx.x / n_split, sp = (int) blockIdx.x % n_split, gq = a->n_head / a->n_head_kv, g = h / gq;
+    const int half = hd >> 1, per_pad = (a->per + 31) & ~31;
+    const int kt = a->kv_type, vt = a->v_type, krb = a->kv_rb, vrb = a->v_rb;
+    // LDS (inside the staging area; every area a multiple of 16 bytes): plan_attn_q80's, the windows with each side's row bytes
+    float * misc = c.stg;                                                      // [16]: 0 maximum, 2 cache slot (int), 8..15 q's block sums (Q8_1: a Q4_1 / Q5_1 K)
+    float * sq = misc + 16, * sk = sq + hd, * sv = sk + hd, * cst = sv + hd;   // q / k / v as polled (q, k roped in place) | cos [hd/2] sin [hd/2]
+    float * qd = cst + hd;                                                     // [8] q's block scales (a block K)
+    uint32_t * qq = (uint32_t *) (qd + 8);                                     // [64] q's packed quants
+    float * sc = (float *) (qq + 64);                                          // [per_pad] mask -> scores -> weights
+    float * msv = sc + per_pad;                                                // [per_pad] rescale factors
+    char * kwin = (char *) (msv + per_pad);                                    // [cnt][krb] K rows
+    char * vwin = kwin + (size_t) per_pad * krb;                               // [cnt][vrb] V rows
+    const int32_t * pos_p = a->pos, * nkv_p = a->n_kv_dev;
+    char * const * kdst_p = a->k_dst, * const * vdst_p = a->v_dst;
+    const int pos = pos_p[0];
+    char * const kdst = *kdst_p, * const vdst = *vdst_p;
+    int n_kv = a->n_kv;
+    if (nkv_p) n_kv = min(n_kv, max(1, nkv_p[0]));
+    const int per = (n_kv + n_split - 1) / n_split;
+    const int j0 = sp * per, j1 = min(n_kv, j0 + per), cnt = max(0, j1 - j0);
+    if (a->entry_barrier) plan_lds_barrier();
+    plan_prefetch_desc(c, wave, lane);
+    PLAN_STAMP(0);
+    unsigned long long exp_tab = 0ull;
+    if (wave == 0) exp_tab = PLAN_EXP2F_T[lane & 31];
+
+    // ---- 0. polls | rope table | window copy ----
+    const int nch = (hd + 127) >> 7, n_poll = 3 * nch, n_tab = (half + 63) >> 6;
+    if (wave < n_poll) {
+        PollCtx pc; pc.sync = c.sync; pc.timeout = c.timeout; pc.t0 = __builtin_amdgcn_s_memrealtime();
+        unsigned spins = 0;
+        const int which = wave / nch, ch = wave % nch;
+        VecSrc vs;
+        if (which == 0)      { vs.plain = a->q.plain; vs.gran = a->q.gran; vs.tag_off = a->q.tag_off; }
+        else if (which == 1) { vs.plain = a->k.plain; vs.gran = a->k.gran; vs.tag_off = a->k.tag_off; }
+        else                 { vs.plain = a->v.plain; vs.gran = a->v.gran; vs.tag_off = a->v.tag_off; }
+        vs.pad = 0;
+        const SrcView s = src_view(vs, (which == 0 ? h : g) * hd, hd, c.epoch);
+        float * dst = which == 0 ? sq : which == 1 ? sk : sv;
+        float v0 = 0.f, v1 = 0.f;
+        bool ok_all = true;
+        for (;;) {
+            const bool ok = src_try(s, ch, lane, v0, v1) || 128 * ch + 2 * lane >= hd;
+            if (__ballot(!ok) == 0ull) break;
+            if (!poll_backoff(pc, spins, lane)) { ok_all = false; break; }
+        }
+        const int e = 128 * ch + 2 * lane;
+        if (ok_all && e < hd) { dst[e] = v0; dst[e + 1] = v1; }
+        if (!ok_all && lane == 0) c.ctl[CTL_OK] = 0;
+    } else if (wave < n_poll + n_tab) {
+        // rope table: plan_attn_lds step 0's (ops_glue.hip k_rope / ggml-cpu/ops.cpp:5088-5270)
+        const int ip = 64 * (wave - n_poll) + lane;
+        const int n_dims = a->n_dims;
+        if (2 * ip < n_dims) {
+            const float * ffp = a->freq_factors;
+            const float ff = ffp ? ffp[ip] : 1.0f;
+            const float tscale = a->theta_scale;
+            float th = (float) pos;
+            const int steps = (n_dims >> 1) - 1;
+#pragma unroll 8
+            for (int j = 0; j < steps; ++j) th = __fmul_rn(th, j < ip ? tscale : 1.0f);
+            const float theta_extrap = __fdiv_rn(th, ff);
+            const float theta_interp = a->freq_scale * theta_extrap;
+            float theta = theta_interp, mscale = a->attn_factor;
+            if (a->ext_factor != 0.0f) {
+                const float y = ((float) ip - a->corr0) / fmaxf(0.001f, a->corr1 - a->corr0);
+                const float ramp_mix = (1.0f - fminf(1.0f, fmaxf(0.0f, y))) * a->ext_factor;
+                theta = theta_interp * (1.0f - ramp_mix) + theta_extrap * ramp_mix;
+                mscale *= 1.0f + 0.1f * logf(1.0f / a->freq_scale);
+            }
+            cst[ip] = cosf(theta) * mscale; cst[half + ip] = sinf(theta) * mscale;
+        }
+        if (wave == n_poll && lane == 0) {
+            const unsigned long long diff = (unsigned long long) (kdst - a->k_cache), np = (unsigned long long) a->k_nb_pos;
+            ((int *) misc)[2] = ((diff | np) >> 32) == 0ull ? (int) ((unsigned) diff / (unsigned) np) : (int) (diff / np);
+        }
+    } else {
+        const int wi = wave - n_poll - n_tab, n_w = GEMV_WAVES - n_poll - n_tab;
+        if (cnt > 0) {
+            const char * kb = a->k_cache + (int64_t) g * a->k_nb_head + (int64_t) j0 * a->k_nb_pos;
+            const char * vb = a->v_cache + (int64_t) g * a->v_nb_head + (int64_t) j0 * a->v_nb_pos;
+            mix_copy_rows(kwin, kb, a->k_nb_pos, cnt, krb, a->kv_unit, wi, n_w, lane);
+            mix_copy_rows(vwin, vb, a->v_nb_pos, cnt, vrb, a->v_unit, wi, n_w, lane);
+        }
+        const char * maskp = a->mask; const int mask_f16 = a->mask_f16;
+        for (int jj = wi * 64 + lane; jj < cnt; jj += n_w * 64)
+            sc[jj] = maskp ? (mask_f16 ? __half2float(((const __half *) maskp)[j0 + jj]) : ((const float *) maskp)[j0 + jj]) : 0.0f;
+    }
+    const int n_dims_r = a->n_dims, neox_r = a->neox, plain_out = a->plain;
+    const float scale_r = a->scale;
+    Granule * const out_gran = a->out_gran, * const part_gran = a->part; float * const out_plain = a->out_plain;
+    const int64_t v_dst_nb = a->v_dst_nb;
+    asm volatile("" :: "s"(n_dims_r), "s"(neox_r), "s"(plain_out), "s"(scale_r), "s"(out_gran), "s"(part_gran), "s"(out_plain), "s"(v_dst_nb));
+    plan_lds_barrier();
+    if (!c.ctl[CTL_OK]) return false;
+    PLAN_STAMP(1);
+
+    // ---- 1. rope of q and k in f32, in place (a thread owns one rotated pair) ----
+    if (tid < hd) {
+        const bool isq = tid < half;
+        float * x = isq ? sq : sk;
+        const int ip = isq ? tid : tid - half, i0 = 2 * ip;
+        if (i0 < n_dims_r) {
+            const float cs = cst[ip], sn = cst[half + ip];
+            const int e0 = neox_r ? ip : i0, e1 = neox_r ? ip + n_dims_r / 2 : i0 + 1;
+            const float x0 = x[e0], x1 = x[e1];
+            x[e0] = x0 * cs - x1 * sn; x[e1] = x0 * sn + x1 * cs;
+        }
+    }
+    plan_lds_barrier();
+    // ---- 2. a block K: q -> its vec_dot_type (wave 0);  this token's K row (wave 1) and V row (wave 2) by their own types: into the cache (one
+    //         workgroup per kv head) and into the window ----
+    const int slot = ((const int *) misc)[2];
+    const bool in_win = slot >= j0 && slot < j1, store = sp == 0 && h % gq == 0;
+    if (wave == 0) {
+        if (kt == MI355Q_TYPE_Q4_1 || kt == MI355Q_TYPE_Q5_1) fa_quantize_q<true>(sq, lane, hd, qq, qd, misc + 8);
+        else if (kt != 1)                                     fa_quantize_q<false>(sq, lane, hd, qq, qd, misc + 8);
+    } else if (wave == 1) {
+        mix_store_row_rt(kt, sk, hd, lane, in_win ? kwin + (size_t) (slot - j0) * krb : nullptr, store ? kdst + (int64_t) g * krb : nullptr, 2);
+    } else if (wave == 2) {
+        // (an f16 V row goes where the f16 stage puts it: element d of head g at v_dst + (g hd + d) v_dst_nb)
+        mix_store_row_rt(vt, sv, hd, lane, in_win ? vwin + (size_t) (slot - j0) * vrb : nullptr,
+                         store ? (vt == 1 ? vdst + (int64_t) g * hd * v_dst_nb : vdst + (int64_t) g * vrb) : nullptr, v_dst_nb);
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(2);
+    // ---- 3. scores by K's type ----
+    switch (kt) {                                                              // (uniform)
+    case 1:                mix_scores<1>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    case MI355Q_TYPE_Q8_0: mix_scores<MI355Q_TYPE_Q8_0>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    case MI355Q_TYPE_Q4_0: mix_scores<MI355Q_TYPE_Q4_0>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    case MI355Q_TYPE_Q4_1: mix_scores<MI355Q_TYPE_Q4_1>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    case MI355Q_TYPE_Q5_0: mix_scores<MI355Q_TYPE_Q5_0>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    case MI355Q_TYPE_Q5_1: mix_scores<MI355Q_TYPE_Q5_1>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    default:               mix_scores<MI355Q_TYPE_IQ4_NL>(kwin, krb, cnt, hd, sq, qd, qq, misc + 8, scale_r, sc, tid, wave, lane); break;
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(3);
+    // ---- 3b. an f16 V over several splits (chain): the CPU's F16-accumulator walk is one chain over the whole window, and no merge of per-split sums
+    //          reproduces its roundings.  The splits score their shares in parallel (above) and then walk one after the other: split sp waits for
+    //          (accumulator [hd], maximum, S) of split sp - 1 -- published below under this stage's tag -- and continues from there.  The last split's
+    //          result is the single walk's, bit for bit, and there is no merge stage.  (sk / sv are free since step 2.)
+    const bool chain = a->chain != 0;                                          // (uniform)
+    float * cin = sk;                                                          // [hd + 2] what the split before left
+    if (chain && sp > 0) {
+        const int n = hd + 2;
+        if (wave < ((n + 127) >> 7)) {
+            VecSrc vs; vs.plain = nullptr; vs.gran = part_gran + (size_t) ((size_t) h * n_split + sp - 1) * n; vs.tag_off = 0; vs.pad = 0;
+            SrcView s = src_view(vs, 0, n, 0); s.expect = tag;
+            PollCtx pc; pc.sync = c.sync; pc.timeout = c.timeout; pc.t0 = __builtin_amdgcn_s_memrealtime();
+            unsigned spins = 0;
+            float v0 = 0.f, v1 = 0.f;
+            bool ok_all = true;
+            for (;;) {
+                const bool ok = src_try(s, wave, lane, v0, v1) || 128 * wave + 2 * lane >= n;
+                if (__ballot(!ok) == 0ull) break;
+                if (!poll_backoff(pc, spins, lane)) { ok_all = false; break; }
+            }
+            const int e = 128 * wave + 2 * lane;
+            if (ok_all && e < n) { cin[e] = v0; cin[e + 1] = v1; }
+            if (!ok_all && lane == 0) c.ctl[CTL_OK] = 0;
+        }
+        plan_lds_barrier();
+        if (!c.ctl[CTL_OK]) return false;
+    }
+    const bool cont = chain && sp > 0;
+    // ---- 4. the online softmax in position order ----
+    if (wave == 0) {
+        const float mx = fa_seq_weights(sc, msv, cnt, lane, exp_tab, cont ? cin[hd] : -INFINITY);
+        if (lane == 0) misc[0] = mx;
+    }
+    plan_lds_barrier();
+    PLAN_STAMP(4);
+    // ---- 5. V . P by V's type; publish ----
+    if (tid < hd) {
+        float acc, S;
+        const bool one = n_split == 1 || (chain && sp == n_split - 1);          // this workgroup holds the head's whole walk
+        const float acc0 = cont ? cin[tid] : 0.0f, S0 = cont ? cin[hd + 1] : 0.0f;
+        switch (vt) {                                                          // (uniform)
+        case 1:                mix_pv<1>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        case MI355Q_TYPE_Q8_0: mix_pv<MI355Q_TYPE_Q8_0>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        case MI355Q_TYPE_Q4_0: mix_pv<MI355Q_TYPE_Q4_0>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        case MI355Q_TYPE_Q4_1: mix_pv<MI355Q_TYPE_Q4_1>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        case MI355Q_TYPE_Q5_0: mix_pv<MI355Q_TYPE_Q5_0>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        case MI355Q_TYPE_Q5_1: mix_pv<MI355Q_TYPE_Q5_1>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        default:               mix_pv<MI355Q_TYPE_IQ4_NL>(vwin, vrb, tid, sc, msv, cnt, acc0, S0, acc, S); break;
+        }
+        if (one) {
+            const float r = __fmul_rn(acc, __fdiv_rn(1.0f, S));
+            publish(out_gran + h * hd + tid, r, tag);
+            if (plain_out) out_plain[h * hd + tid] = r;
+        } else {
+            Granule * part = part_gran + (size_t) ((size_t) h * n_split + sp) * (hd + 2);
+            publish(part + tid, acc, tag);
+            if (tid == 0) { publish(part + hd, misc[0], tag); publish(part + hd + 1, S, tag); }
+        }
+    }
+    PLAN_STAMP(5);
+    return true;
+}
+
 // merge the KV splits of a head: out = sum_s e^{m_s - M} o_s / sum_s e^{m_s - M} l_s     (workgroup h * n_split does head h)
 static __device__ __noinline__ bool plan_attn_combine(AttnC a_in, const StageCtx & c_in, unsigned tag_in) {
     const AttnC a = (AttnC) (uintptr_t) uniform_ptr((const void *) (uintptr_t) a_in);
@@ -1629,7 +1935,8 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
             }
         } else if (kind == PLAN_K_ATTN) {
             const int af = st->flags;
-            if (af & PLAN_F_ATTN_Q) {
+            if (af & PLAN_F_ATTN_MIX) ok = plan_attn_mix((AttnC) st->attn, c, epoch + st->tag_off);
+            else if (af & PLAN_F_ATTN_Q) {
                 switch (((AttnC) st->attn)->kv_type) {
                 case MI355Q_TYPE_Q8_0: ok = plan_attn_q80<MI355Q_TYPE_Q8_0>((AttnC) st->attn, c, epoch + st->tag_off); break;
                 case MI355Q_TYPE_Q4_0: ok = plan_attn_q80<MI355Q_TYPE_Q4_0>((AttnC) st->attn, c, epoch + st->tag_off); break;
@@ -1650,6 +1957,7 @@ k_plan(const PlanStage * stages_g, int n_stages, unsigned * sync, int even, unsi
 // ------------------------------------------------------------------------------------------------
 // host side
 static const char * plan_kv_name(int t) {
+    if (t == 1 || t == 0) return "f16";
     return t == MI355Q_TYPE_Q8_0 ? "q8_0" : t == MI355Q_TYPE_Q4_0 ? "q4_0" : t == MI355Q_TYPE_Q4_1 ? "q4_1" : t == MI355Q_TYPE_Q5_0 ? "q5_0" : t == MI355Q_TYPE_Q5_1 ? "q5_1" : "iq4_nl";
 }
 // ------------------------------------------------------------------------------------------------
@@ -1774,17 +2082,38 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
         const mi355q_stage & in = stages[s];
         if (in.kind == MI355Q_STAGE_ATTN) {
             const mi355q_attn * at = in.attn;
+            // the cache types: MI355Q_STAGE_KV_* name both sides, or K's alone when a MI355Q_STAGE_KVV_* bit names V's (1 = f16)
+            const int kvq = in.flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL);
+            const int kvv = in.flags & (MI355Q_STAGE_KVV_F16 | MI355Q_STAGE_KVV_Q8_0 | MI355Q_STAGE_KVV_Q4_0 | MI355Q_STAGE_KVV_Q4_1 | MI355Q_STAGE_KVV_Q5_0 | MI355Q_STAGE_KVV_Q5_1 | MI355Q_STAGE_KVV_IQ4_NL);
+            if (kvq & (kvq - 1)) { mi355q_set_error("plan_create: attn stage: more than one MI355Q_STAGE_KV_* flag set"); return MI355Q_ERR_UNSUPPORTED; }
+            if (kvv & (kvv - 1)) { mi355q_set_error("plan_create: attn stage: more than one MI355Q_STAGE_KVV_* flag set"); return MI355Q_ERR_UNSUPPORTED; }
+            const int kv_type = kvq == MI355Q_STAGE_KV_Q8_0 ? MI355Q_TYPE_Q8_0 : kvq == MI355Q_STAGE_KV_Q4_0 ? MI355Q_TYPE_Q4_0 : kvq == MI355Q_STAGE_KV_Q4_1 ? MI355Q_TYPE_Q4_1 :
+                                kvq == MI355Q_STAGE_KV_Q5_0 ? MI355Q_TYPE_Q5_0 : kvq == MI355Q_STAGE_KV_Q5_1 ? MI355Q_TYPE_Q5_1 : kvq == MI355Q_STAGE_KV_IQ4_NL ? MI355Q_TYPE_IQ4_NL : 0;
+            const int k_side = kv_type ? kv_type : 1;
+            const int v_side = kvv == MI355Q_STAGE_KVV_F16 ? 1 : kvv == MI355Q_STAGE_KVV_Q8_0 ? MI355Q_TYPE_Q8_0 : kvv == MI355Q_STAGE_KVV_Q4_0 ? MI355Q_TYPE_Q4_0 : kvv == MI355Q_STAGE_KVV_Q4_1 ? MI355Q_TYPE_Q4_1 :
+                               kvv == MI355Q_STAGE_KVV_Q5_0 ? MI355Q_TYPE_Q5_0 : kvv == MI355Q_STAGE_KVV_Q5_1 ? MI355Q_TYPE_Q5_1 : kvv == MI355Q_STAGE_KVV_IQ4_NL ? MI355Q_TYPE_IQ4_NL : k_side;
+            const bool mixed = v_side != k_side;               // (a V bit equal to K's type: the same-type stage, as without the bit)
+            if (mixed && at && at->head_dim % 32) {
+                char msg[200];
+                snprintf(msg, sizeof(msg), "plan_create: attn stage: a %s / %s KV cache needs head_dim %% 32 == 0 (whole 32-element blocks), not %d", plan_kv_name(k_side), plan_kv_name(v_side), at->head_dim);
+                mi355q_set_error(msg); return MI355Q_ERR_UNSUPPORTED;
+            }
             if (!at || !at->q || !at->k || !at->v || !at->pos || !at->k_cache || !at->v_cache || !at->k_dst || !at->v_dst || !at->out) { mi355q_set_error("plan_create: attn stage: null pointer"); return MI355Q_ERR_SHAPE; }
             if (at->n_head < 1 || at->n_head_kv < 1 || at->n_head % at->n_head_kv || at->head_dim < 32 || at->head_dim > 256 || at->head_dim % 32 || at->n_kv < 1) { mi355q_set_error("plan_create: attn stage: bad head geometry"); return MI355Q_ERR_SHAPE; }
             if (at->rope.mode != 0 && at->rope.mode != 2) { mi355q_set_error("plan_create: attn stage: rope mode must be 0 or 2"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->rope.n_dims <= 0 || at->rope.n_dims % 2 || at->rope.n_dims > at->head_dim) { mi355q_set_error("plan_create: attn stage: rope n_dims"); return MI355Q_ERR_SHAPE; }
-            const int kvq = in.flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL);
-            if (kvq & (kvq - 1)) { mi355q_set_error("plan_create: attn stage: more than one MI355Q_STAGE_KV_* flag set"); return MI355Q_ERR_UNSUPPORTED; }
-            const int kv_type = kvq == MI355Q_STAGE_KV_Q8_0 ? MI355Q_TYPE_Q8_0 : kvq == MI355Q_STAGE_KV_Q4_0 ? MI355Q_TYPE_Q4_0 : kvq == MI355Q_STAGE_KV_Q4_1 ? MI355Q_TYPE_Q4_1 :
-                                kvq == MI355Q_STAGE_KV_Q5_0 ? MI355Q_TYPE_Q5_0 : kvq == MI355Q_STAGE_KV_Q5_1 ? MI355Q_TYPE_Q5_1 : kvq == MI355Q_STAGE_KV_IQ4_NL ? MI355Q_TYPE_IQ4_NL : 0;
             const int kv_bb = kv_block_bytes_rt(kv_type);
-            if (kvq && at->v_nb_dim != kv_bb) { mi355q_set_error("plan_create: attn stage: a quantized cache needs the flash layout (V rows per position, v_nb_dim = block bytes); the transposed V cache is not supported"); return MI355Q_ERR_UNSUPPORTED; }
-            if (!kvq && at->v_nb_dim != 2 && at->v_nb_pos != 2) { mi355q_set_error("plan_create: attn stage: V cache must be contiguous along head_dim or along positions"); return MI355Q_ERR_UNSUPPORTED; }
+            if (mixed) {                                       // each side in its own flash layout: V rows per position, v_nb_dim = V's block bytes (f16: 2)
+                const int v_bb = v_side == 1 ? 2 : kv_block_bytes_rt(v_side);
+                if (at->v_nb_dim != v_bb) {
+                    char msg[256];
+                    snprintf(msg, sizeof(msg), "plan_create: attn stage: a %s / %s KV cache needs the flash layout (V rows per position, v_nb_dim = %d for a %s V); the transposed V cache is not supported",
+                             plan_kv_name(k_side), plan_kv_name(v_side), v_bb, plan_kv_name(v_side));
+                    mi355q_set_error(msg); return MI355Q_ERR_UNSUPPORTED;
+                }
+            }
+            else if (kvq && at->v_nb_dim != kv_bb) { mi355q_set_error("plan_create: attn stage: a quantized cache needs the flash layout (V rows per position, v_nb_dim = block bytes); the transposed V cache is not supported"); return MI355Q_ERR_UNSUPPORTED; }
+            if (!mixed && !kvq && at->v_nb_dim != 2 && at->v_nb_pos != 2) { mi355q_set_error("plan_create: attn stage: V cache must be contiguous along head_dim or along positions"); return MI355Q_ERR_UNSUPPORTED; }
             if (at->n_head > n_cu) { mi355q_set_error("plan_create: attn stage: more heads than CUs"); return MI355Q_ERR_UNSUPPORTED; }
             AttnStage A = {};
             const int hd = at->head_dim;
@@ -1793,6 +2122,21 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             A.k_nb_pos = at->k_nb_pos; A.k_nb_head = at->k_nb_head; A.v_nb_pos = at->v_nb_pos; A.v_nb_dim = at->v_nb_dim; A.v_nb_head = at->v_nb_head; A.v_dst_nb = at->v_dst_nb;
             A.k_dst = (char * const *) at->k_dst; A.v_dst = (char * const *) at->v_dst; A.mask = (const char *) at->mask; A.mask_f16 = at->mask_f16;
             A.n_head = at->n_head; A.n_head_kv = at->n_head_kv; A.hd = hd; A.n_kv = at->n_kv; A.scale = at->scale;
+            if (mixed) {                                       // per side: bytes per head row (f16: 2 hd), the widest copy unit its addresses and strides allow; a block side must be even
+                A.mixed = 1; A.kv_type = k_side; A.v_type = v_side;
+                A.kv_rb = k_side == 1 ? 2 * hd : hd / 32 * kv_block_bytes_rt(k_side);
+                A.v_rb  = v_side == 1 ? 2 * hd : hd / 32 * kv_block_bytes_rt(v_side);
+                const uint64_t any_k = (uint64_t) (uintptr_t) at->k_cache | (uint64_t) at->k_nb_pos | (uint64_t) at->k_nb_head | (uint64_t) A.kv_rb;
+                const uint64_t any_v = (uint64_t) (uintptr_t) at->v_cache | (uint64_t) at->v_nb_pos | (uint64_t) at->v_nb_head | (uint64_t) A.v_rb;
+                auto unit_of = [](uint64_t any) { return (any & 7) == 0 ? 8 : (any & 3) == 0 ? 4 : 2; };
+                A.kv_unit = unit_of(any_k); A.v_unit = unit_of(any_v);
+                if (v_side == 1 && (at->v_dst_nb < 2 || (at->v_dst_nb & 1))) { mi355q_set_error("plan_create: attn stage: an f16 V side stores this token's row through v_dst_nb (bytes between elements: even, >= 2)"); return MI355Q_ERR_UNSUPPORTED; }
+                if ((any_k | any_v) & 1) {
+                    char msg[200];
+                    snprintf(msg, sizeof(msg), "plan_create: attn stage: the addresses and strides of a %s / %s KV cache must be even (the %s side's are not)", plan_kv_name(k_side), plan_kv_name(v_side), (any_k & 1) ? "K" : "V");
+                    mi355q_set_error(msg); return MI355Q_ERR_UNSUPPORTED;
+                }
+            } else
             if (kvq) {                                         // a quantized cache: rows of hd / 32 blocks, copied into LDS in the widest unit every address allows
                 A.kv_type = kv_type; A.kv_rb = hd / 32 * kv_bb;
                 const uint64_t any = (uint64_t) (uintptr_t) at->k_cache | (uint64_t) (uintptr_t) at->v_cache | (uint64_t) at->k_nb_pos | (uint64_t) at->k_nb_head |
@@ -1816,7 +2160,11 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             }
             // internal stages: attention per (head, split) and, when the heads are split, the merge
             PlanStage p = {}; p.kind = PLAN_K_ATTN; p.tag_off = (unsigned) v.size() + 1; p.flags = PLAN_F_NEW_X;
-            if (A.n_split == 1) {
+            A.chain = mixed && v_side == 1 && A.n_split > 1;      // an f16 V over several splits: walked split after split (plan_attn_mix 3b), no merge stage
+            // (split sp waits INSIDE the stage for split sp - 1: that relies on all n_head * n_split workgroups of the stage being resident at once, which
+            //  holds because n_head * n_split <= #CU and the launch is one workgroup per CU, all co-resident -- see mi355q_regs_plan_run; the wait is a bounded poll)
+            if (A.n_split == 1 || A.chain) {
+                if (A.chain) { const size_t part_off = gran_count; gran_count += (size_t) at->n_head * A.n_split * (hd + 2); gran_count = (gran_count + 1) & ~(size_t) 1; A.part = (Granule *) (uintptr_t) (part_off + 1); }
                 A.out_gran = (Granule *) (uintptr_t) (new_out(at->out, (int64_t) at->n_head * hd, p.tag_off, at->out_id) + 1);
                 v.push_back(p); attn_of.push_back((int) va.size());
             } else {
@@ -1832,7 +2180,8 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             const size_t need2 = (size_t) 4 * A.n_split * (hd + 2) + 64;
             if (need > stg_max) stg_max = need;
             if (need2 > stg_max) stg_max = need2;
-            bytes += (int64_t) 2 * at->n_kv * at->n_head_kv * (kvq ? A.kv_rb / hd : 2) * hd;
+            if (mixed) bytes += (int64_t) at->n_kv * at->n_head_kv * (A.kv_rb + A.v_rb);
+            else bytes += (int64_t) 2 * at->n_kv * at->n_head_kv * (kvq ? A.kv_rb / hd : 2) * hd;
             continue;
         }
         if (in.kind != MI355Q_STAGE_GEMV) { mi355q_set_error("plan_create: unknown stage kind"); return MI355Q_ERR_UNSUPPORTED; }
@@ -1964,6 +2313,23 @@ int mi355q_regs_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int
             AttnStage & A = va[attn_of[si]];
             const int per_pad = (A.per + 31) & ~31;
             A.entry_barrier = si == 0 || v[si - 1].kind != PLAN_K_GEMV;
+            if (A.mixed) {
+                // mixed K / V types always run from LDS (plan_attn_mix): plan_attn_q80's vectors, 8 bytes of scores per position and the two windows of
+                // k_rb + v_rb bytes per position (a block side: hd / 32 x its block bytes; an f16 side: 2 hd).  A window beyond that is refused.
+                const size_t vecs = (size_t) 4 * (16 + 4 * A.hd + 72), per_pos = 8 + (size_t) A.kv_rb + (size_t) A.v_rb;
+                const size_t need = vecs + per_pos * per_pad + 64;
+                if (fixed + ((std::max(need, stg_max) + 15) & ~(size_t) 15) > cap) {
+                    const size_t room = cap - fixed - 64 - vecs;
+                    char msg[240];
+                    snprintf(msg, sizeof(msg), "plan_create: attn stage: a %s / %s KV window of %d positions per split (%d split(s)) does not fit the LDS: at most %zu positions per split",
+                             plan_kv_name(A.kv_type), plan_kv_name(A.v_type), A.per, A.n_split, (room / per_pos) & ~(size_t) 31);
+                    mi355q_set_error(msg);
+                    return MI355Q_ERR_UNSUPPORTED;
+                }
+                v[si].flags |= PLAN_F_ATTN_MIX; if (need > stg_max) stg_max = need;
+                if (getenv("MI355Q_PLAN_VERBOSE")) fprintf(stderr, "mi355q plan: attention stage %zu: n_kv %d, %d split(s) of %d positions, %s / %s cache, window in LDS (%zu bytes, %zu fixed, %d- / %d-byte copies)\n", si, A.n_kv, A.n_split, A.per, plan_kv_name(A.kv_type), plan_kv_name(A.v_type), need, fixed, A.kv_unit, A.v_unit);
+                continue;
+            }
             if (A.kv_type) {
                 // a quantized cache always runs from LDS (plan_attn_q80): 21 hd + 352 bytes of vectors, 8 bytes of scores per position and the K / V
                 // windows of 2 x rb bytes per position (rb = hd / 32 x the type's block bytes: 34, 18, 20, 22, 24, 18).  A window beyond that is refused: the caller falls back to the node ops.

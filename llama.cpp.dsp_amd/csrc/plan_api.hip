@@ -36,11 +36,15 @@ namespace { struct Handle { int ring; mi355q_plan * impl; }; }
 int mi355q_plan_create(mi355q_plan ** out, const mi355q_stage * stages, int n_stages, int flags) {
     if (!out) { mi355q_set_error("plan_create: null argument"); return MI355Q_ERR_SHAPE; }
     static const int want_ring = [] { const char * e = getenv("MI355Q_PLAN_ENGINE"); return e && strcmp(e, "ring") == 0 ? 1 : 0; }();
-    if (want_ring && stages)                                   // plan_ring.hip has no quantized-cache attention stage: it would read the blocks as f16
-        for (int i = 0; i < n_stages; ++i)
-            if (stages[i].kind == MI355Q_STAGE_ATTN && (stages[i].flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL))) {
-                mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for a quantized (q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl) KV cache"); return MI355Q_ERR_UNSUPPORTED;
-            }
+    if (want_ring && stages)                                   // plan_ring.hip has no quantized-cache attention stage (it would read the blocks as f16) and none for mixed K / V types
+        for (int i = 0; i < n_stages; ++i) {
+            if (stages[i].kind != MI355Q_STAGE_ATTN) continue;
+            const int kb = stages[i].flags & (MI355Q_STAGE_KV_Q8_0 | MI355Q_STAGE_KV_Q4_0 | MI355Q_STAGE_KV_Q4_1 | MI355Q_STAGE_KV_Q5_0 | MI355Q_STAGE_KV_Q5_1 | MI355Q_STAGE_KV_IQ4_NL);
+            const int vb = stages[i].flags & (MI355Q_STAGE_KVV_F16 | MI355Q_STAGE_KVV_Q8_0 | MI355Q_STAGE_KVV_Q4_0 | MI355Q_STAGE_KVV_Q4_1 | MI355Q_STAGE_KVV_Q5_0 | MI355Q_STAGE_KVV_Q5_1 | MI355Q_STAGE_KVV_IQ4_NL);
+            if (kb && vb) { mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for mixed K / V cache types (nor for a quantized KV cache)"); return MI355Q_ERR_UNSUPPORTED; }
+            if (kb) { mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for a quantized (q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl) KV cache"); return MI355Q_ERR_UNSUPPORTED; }
+            if (vb && vb != MI355Q_STAGE_KVV_F16) { mi355q_set_error("plan_create: the ring engine (MI355Q_PLAN_ENGINE=ring) has no attention stage for mixed K / V cache types"); return MI355Q_ERR_UNSUPPORTED; }   // (an f16 K with a block V)
+        }
     mi355q_plan * impl = nullptr;
     const int rc = want_ring ? mi355q_ring_plan_create(&impl, stages, n_stages, flags) : mi355q_regs_plan_create(&impl, stages, n_stages, flags);
     if (rc != MI355Q_OK) return rc;

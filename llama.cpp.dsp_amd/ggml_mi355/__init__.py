@@ -317,6 +317,7 @@ def mul_mat_multi(ws_: list, x, outs=None, flags: int = 0):
 
 
 _STAGE_KV = {"f16": 0, "q8_0": 0x4, "q4_0": 0x8, "q4_1": 0x10, "q5_0": 0x20, "q5_1": 0x40, "iq4_nl": 0x80}     # mi355q_stage.flags of an ATTN stage: MI355Q_STAGE_KV_*
+_STAGE_KVV = {"f16": 0x100, "q8_0": 0x200, "q4_0": 0x400, "q4_1": 0x800, "q5_0": 0x1000, "q5_1": 0x2000, "iq4_nl": 0x4000}     # ... MI355Q_STAGE_KVV_*: V's type where a stage names it (kv_v=)
 KV_BLOCK = {"q8_0": (34, Q8_0), "q4_0": (18, Q4_0), "q4_1": (20, Q4_1), "q5_0": (22, Q5_0), "q5_1": (24, Q5_1), "iq4_nl": (18, IQ4_NL)}     # cache type -> (bytes per 32-element block, type id)
 
 
@@ -344,10 +345,13 @@ def _stage_array(stages):
             at.mask_f16 = 1 if (a.get("mask") is not None and a["mask"].dtype == torch.float16) else 0
             at.scale = float(a["scale"])
             st.kind = STAGE_ATTN; st.attn = C.pointer(at); st.flags = STAGE_NO_PLAIN if sd.get("no_plain") else 0
-            kv = a.get("kv", "f16")
-            if kv not in _STAGE_KV:
-                raise ValueError(f"attn kv must be one of {sorted(_STAGE_KV)}, not {kv!r}")
-            st.flags |= _STAGE_KV[kv]
+            kv, kv_v = a.get("kv", "f16"), a.get("kv_v")
+            for name, val, table in (("kv", kv, _STAGE_KV), ("kv_v", kv_v, _STAGE_KVV)):
+                if val in ("bf16", "bfloat16"):
+                    raise ValueError(f"attn {name}: the plan has no attention stage for a bf16 cache side (one of {sorted(table)})")
+                if val not in table and not (name == "kv_v" and val is None):
+                    raise ValueError(f"attn {name} must be one of {sorted(table)}, not {val!r}")
+            st.flags |= _STAGE_KV[kv] | (_STAGE_KVV[kv_v] if kv_v is not None else 0)
             keep.append((a, at))
         else:
             if isinstance(sd, dict):
@@ -391,9 +395,13 @@ class Plan:
       * dict(attn=dict(q=, k=, v=, pos=, rope=dict(n_dims=, mode=0, n_ctx_orig=0, freq_base=10000.0, freq_scale=1.0, ext_factor=0.0,
                        attn_factor=1.0, beta_fast=32.0, beta_slow=1.0), freq_factors=None, k_cache=, v_cache=, k_nb_pos=, k_nb_head=, v_nb_pos=,
                        v_nb_dim=, v_nb_head=, k_dst=, v_dst= (int64 device tensors holding the destination ADDRESSES), v_dst_nb=, mask=None,
-                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16", q_id=0, k_id=0, v_id=0, out_id=0), no_plain=False)
+                       n_head=, n_head_kv=, head_dim=, n_kv=, scale=, out=, kv="f16", kv_v=None, q_id=0, k_id=0, v_id=0, out_id=0), no_plain=False)
         -- see include/mi355q.h mi355q_attn;
         kv="q8_0" / "q4_0" / "q4_1" / "q5_0" / "q5_1" / "iq4_nl": the caches hold blocks of that type (uint8 tensors; MI355Q_STAGE_KV_*, flash layout only).
+        kv_v= names V's type where it differs from K's (MI355Q_STAGE_KVV_*; None: the same as kv; "f16" is allowed on either side): `kv` is then K's
+        type alone, each side keeps its own layout (a block side: uint8 block rows, v_nb_dim = its block bytes; an f16 side: f16 rows per position,
+        v_nb_dim = 2, the V row stored through v_dst_nb), flash layout only, regs engine only.  kv_v equal to kv is the same-type stage.
+        Unknown names raise ValueError; there is no stage for a bf16 side.
     The tensors are referenced by address: keep them alive (the Plan holds references) and do not move them."""
 
     def __init__(self, stages, flags: int = 0):
