@@ -460,6 +460,29 @@ int mi355q_op_soft_max(const mi355q_tensor *a, const mi355q_tensor *mask, const 
 int mi355q_op_rope(const mi355q_tensor *a, const int32_t *pos, const float *freq_factors, const mi355q_tensor *dst,
                    const mi355q_rope_params *p, void *stream);
 int mi355q_op_mul_mat_f(const mi355q_tensor *a, const mi355q_tensor *b, const mi355q_tensor *dst, void *stream);
+/* Token generation over an UNQUANTIZED weight matrix: y[n][m] = w[m][:] . x[n][:], w an f16 (type 1) or bf16 (type 30) matrix of m rows of
+ * k elements, x f32 with 1 <= n <= 8 rows, y f32; strides in bytes.  One streaming launch: 16-byte non-temporal loads, x rounded once per workgroup
+ * into the weight's type.  The bits are the reference CPU backend's (AVX2 build): x rounded to f16 (nearest even) and ggml_vec_dot_f16, or x rounded by
+ * ggml_compute_fp32_to_bf16 and ggml_vec_dot_bf16 -- for bf16 the same bits as mi355q_op_mul_mat_f.  Asynchronous, capturable, no workspace.
+ * Scope: k % 32 == 0 (the tail the CPU adds in double stays with mi355q_op_mul_mat_f), w and w_stride_bytes multiples of 16 with w_stride_bytes >= 2 k,
+ * x and x_stride_bytes multiples of 4 (x_stride_bytes >= 4 k where n > 1), y and y_stride_bytes multiples of 4 with y_stride_bytes >= 4 m, m >= 1.
+ * Also refused, because measured slower than mi355q_op_mul_mat_f (profiles/fw_stream.md): n >= 4 with m < 8192 and m k >= 2^24.
+ * Everything else: MI355Q_ERR_UNSUPPORTED, nothing launched.  These are not types of the quantized path: mi355q_type_supported(1 / 30) stays 0.
+ * flags: MI355Q_FW_ROWS_* fixes the rows one wave carries (four lanes own a row: 16 fills the wave; fewer spread a short matrix over more CUs);
+ * 0 = the library chooses the largest of 16 / 8 / 4 that still gives each of the 256 CUs a workgroup of MI355Q_FW_WAVES waves.  Every form gives the same bits.
+ * mi355q_mul_mat_fw_path answers MI355Q_FW_PATH_STREAM or MI355Q_ERR_UNSUPPORTED (the message set) from the numbers alone: no device call, nothing
+ * dereferenced; mi355q_mul_mat_fw decides by calling it.  Added without a change of MI355Q_API_VERSION: probe the symbols.                          */
+#define MI355Q_FW_PATH_STREAM 0
+#define MI355Q_FW_WAVES       4
+#define MI355Q_FW_ROWS_AUTO   0x0
+#define MI355Q_FW_ROWS_4      0x1
+#define MI355Q_FW_ROWS_8      0x2
+#define MI355Q_FW_ROWS_16     0x3
+#define MI355Q_FW_ROWS_MASK   0x3
+int mi355q_mul_mat_fw_path(int type, const void *w, int64_t w_stride_bytes, const float *x, int64_t x_stride_bytes, float *y, int64_t y_stride_bytes,
+                           int64_t m, int64_t n, int64_t k, int flags);
+int mi355q_mul_mat_fw(int type /* 1 = f16, 30 = bf16 */, const void *w, int64_t w_stride_bytes, const float *x, int64_t x_stride_bytes,
+                      float *y, int64_t y_stride_bytes, int64_t m, int64_t n, int64_t k, int flags, void *stream);
 /* GGML_OP_GET_ROWS: dst[:, i10, i11, i12] = a[:, ids[i10, i11, i12], i11, i12]; a f32/f16, ids i32 (tensor with type field ignored), dst f32.
  * GGML_OP_SCALE:    dst = a * scale (f32). */
 /* op_cpy whose destination base pointer is read ON THE DEVICE from dest_table[index] (dst->data is ignored): lets a captured

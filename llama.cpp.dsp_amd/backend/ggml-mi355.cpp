@@ -102,6 +102,7 @@ struct mi355_backend_ctx {
     unsigned *  plan_abort = nullptr;   // pinned host word: != 0 once a plan's poll timed out
     bool        plans_disabled = false;
     long        n_planned = 0, n_plans_built = 0;
+    long        n_fw_streamed = 0;      // MUL_MAT nodes with an f16 / bf16 weight matrix that went to mi355q_mul_mat_fw
 };
 constexpr int MI355_MAX_CPY_DESTS = 4096;
 
@@ -343,6 +344,7 @@ static void mi355_backend_free(ggml_backend_t backend) {
                 ctx->n_fused_norm, ctx->n_fused_mats, ctx->n_fused_act, ctx->n_elided_cont, ctx->n_fused_add);
     }
     if (getenv("MI355_GRAPH_STATS")) fprintf(stderr, "MI355 decode plans: %ld graph_compute calls ran as one persistent launch, %ld plans built\n", ctx->n_planned, ctx->n_plans_built);
+    if (getenv("MI355_GRAPH_STATS")) fprintf(stderr, "MI355 float-weight GEMV: %ld MUL_MAT nodes streamed\n", ctx->n_fw_streamed);
     for (mi355_plan_entry * e : ctx->plans) { mi355q_plan_destroy(e->plan); delete e; }
     if (ctx->plan_abort) mi355q_host_free(ctx->plan_abort);
     if (ctx->dest_pinned) mi355q_host_free(ctx->dest_pinned);
@@ -519,6 +521,16 @@ static void mi355_glue_op(mi355_backend_ctx * ctx, struct ggml_tensor * dst, int
     } break;
     case GGML_OP_MUL_MAT: {                                   // f16 / bf16 / f32 src0 or a quantized KV-cache view (quantized weights go through mi355_mul_mat)
         const mi355q_tensor b = mi355_td(dst->src[1]);
+        // a 2-D f16 / bf16 weight matrix under 1 - 8 columns: the streaming GEMV (mi355q_mul_mat_fw, the same CPU bits; MI355_FW_STREAM=0 keeps the old route).
+        // One launch, no workspace, no synchronization: it is captured like the call below.
+        static const bool fw_stream = !(getenv("MI355_FW_STREAM") && atoi(getenv("MI355_FW_STREAM")) == 0);
+        if (fw_stream && (a.type == MI355Q_T_F16 || a.type == MI355Q_T_BF16) && b.type == MI355Q_T_F32 && d.type == MI355Q_T_F32 &&
+            a.ne[2] == 1 && a.ne[3] == 1 && b.ne[2] == 1 && b.ne[3] == 1 && a.nb[0] == 2 && b.nb[0] == 4 && d.nb[0] == 4 && a.ne[0] == b.ne[0] &&
+            mi355q_mul_mat_fw_path(a.type, a.data, a.nb[1], (const float *) b.data, b.nb[1], (float *) d.data, d.nb[1], a.ne[1], b.ne[1], a.ne[0], 0) == MI355Q_FW_PATH_STREAM) {
+            MQ_CHECK(mi355q_mul_mat_fw(a.type, a.data, a.nb[1], (const float *) b.data, b.nb[1], (float *) d.data, d.nb[1], a.ne[1], b.ne[1], a.ne[0], 0, ctx->stream));
+            ++ctx->n_fw_streamed;
+            break;
+        }
         MQ_CHECK(mi355q_op_mul_mat_f(&a, &b, &d, ctx->stream));
     } break;
     default: GGML_ABORT("mi355_glue_op: unexpected op");

@@ -60,7 +60,14 @@ ABI_SYMBOLS = [
     "mi355q_graph_capture_begin", "mi355q_graph_capture_end", "mi355q_graph_launch", "mi355q_graph_destroy",
     "mi355q_op_add_rms_norm_mul", "mi355q_op_unary_mul", "mi355q_op_flash_attn_ext", "mi355q_op_flash_attn_ext_workspace",
     "mi355q_op_flash_attn_ext_path", "mi355q_op_flash_attn_ext_path2", "mi355q_op_flash_attn_ext2",
+    "mi355q_mul_mat_fw", "mi355q_mul_mat_fw_path",
 ]
+
+# mi355q_mul_mat_fw: the streaming GEMV over f16 / bf16 weight matrices (include/mi355q.h MI355Q_FW_*)
+FW_PATH_STREAM = 0
+FW_WAVES = 4                                   # waves per workgroup
+FW_ROWS_AUTO, FW_ROWS_4, FW_ROWS_8, FW_ROWS_16 = 0, 1, 2, 3
+FW_ROWS_PER_WAVE = {FW_ROWS_4: 4, FW_ROWS_8: 8, FW_ROWS_16: 16}      # flag -> rows one wave carries (four lanes own a row)
 
 # mi355q_op_flash_attn_ext_path: which kernels a FLASH_ATTN_EXT call takes (include/mi355q.h MI355Q_FA_PATH_*)
 FA_PATH_ROW_SEQ, FA_PATH_ROW_F32, FA_PATH_ROW_SPLIT, FA_PATH_KV_ROW, FA_PATH_MFMA3, FA_PATH_FUSED, FA_PATH_FUSED_KV = range(7)
@@ -168,6 +175,9 @@ def lib() -> C.CDLL:
     L.mi355q_op_soft_max.argtypes = [TP, TP, TP, C.c_float, C.c_float, vp]
     L.mi355q_op_rope.argtypes = [TP, vp, vp, TP, C.POINTER(_RopeParams), vp]
     L.mi355q_op_mul_mat_f.argtypes = [TP, TP, TP, vp]
+    if hasattr(L, "mi355q_mul_mat_fw"):
+        L.mi355q_mul_mat_fw_path.argtypes = [i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32]
+        L.mi355q_mul_mat_fw.argtypes = [i32, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, vp]
     L.mi355q_op_get_rows.argtypes = [TP, TP, TP, vp]
     L.mi355q_op_scale.argtypes = [TP, TP, C.c_float, vp]
     L.mi355q_op_argsort.argtypes = [TP, TP, i32, vp]
@@ -681,6 +691,33 @@ def op_mul_mat_f(a, b, out=None, kv: str = "q8_0"):
         out = torch.empty(tuple(b.shape[:-2]) + (b.shape[-2], a.shape[-2]), dtype=torch.float32, device=b.device)
     td_a = _td_q8_0(a, kv) if a.dtype == torch.uint8 else _td(a)
     _check(lib().mi355q_op_mul_mat_f(C.byref(td_a), C.byref(_td(b)), C.byref(_td(out)), _stream(torch)), "op_mul_mat_f")
+    return out
+
+
+def mul_mat_fw_path(type_code: int, w: int, w_stride_bytes: int, x: int, x_stride_bytes: int, y: int, y_stride_bytes: int, m: int, n: int, k: int,
+                    flags: int = 0) -> int:
+    """What mi355q_mul_mat_fw would do with these numbers (addresses are plain integers, nothing is read): FW_PATH_STREAM or the negative error
+    code the call would return (last_error() has the message).  No device work."""
+    return int(lib().mi355q_mul_mat_fw_path(type_code, w, w_stride_bytes, x, x_stride_bytes, y, y_stride_bytes, m, n, k, flags))
+
+
+def mul_mat_fw(w, x, out=None, flags: int = 0, w_stride_bytes=None, x_stride_bytes=None, y_stride_bytes=None):
+    """y[N, M] = x[N, K] . w[M, K]^T over an UNQUANTIZED weight matrix with the CPU's bits: w a torch f16 / bf16 2-D tensor or a strided view of
+    one, x f32 [N, K] with 1 <= N <= 8, out f32 [N, M] (its row pitch may be wider).  Raises Mi355qError where mi355q_mul_mat_fw refuses (nothing is
+    launched, `out` is left alone).  `flags`: FW_ROWS_*.  The *_stride_bytes override what the tensors say (pitches torch cannot express)."""
+    torch = _torch()
+    code = {torch.float16: 1, torch.bfloat16: 30, torch.float32: 0}.get(w.dtype)
+    if code is None or w.dim() != 2 or x.dim() != 2 or x.dtype != torch.float32 or w.stride(1) != 1 or (x.shape[1] > 1 and x.stride(1) != 1) or x.shape[1] != w.shape[1]:
+        raise Mi355qError("mul_mat_fw: w must be a 2-D f16 / bf16 tensor with contiguous rows, x f32 [N, K] with contiguous rows")
+    M, K = w.shape
+    N = x.shape[0]
+    if out is None:
+        out = torch.empty((N, M), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape == (N, M) and (M == 1 or out.stride(1) == 1)
+    ws = w.stride(0) * w.element_size() if w_stride_bytes is None else w_stride_bytes
+    xs = x.stride(0) * 4 if x_stride_bytes is None else x_stride_bytes
+    ys = out.stride(0) * 4 if y_stride_bytes is None else y_stride_bytes
+    _check(lib().mi355q_mul_mat_fw(code, w.data_ptr(), ws, x.data_ptr(), xs, out.data_ptr(), ys, M, N, K, flags, _stream(torch)), "mul_mat_fw")
     return out
 
 
